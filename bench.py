@@ -16,6 +16,11 @@ process then also times 16 samples PER GPU and reports it as `weak_scaling` (glo
 between Gmain and Dmain).
 Gradients are exchanged with RCCL all-reduce over xGMI, bucketed and overlapped with the backward graphs.
 
+A plain run times the headline step only: set-up, --warmup steps, --steps timed steps, the outputs (--dump-outputs DIR), the line.
+--full adds everything else the line can carry: the other configurations above (reference call pattern, trunk sharing per phase,
+f32 MFMA only, 2 samples per GPU at N = 1; weak scaling and the exchange-free references at N > 1), the engine roofline with the
+named-kernel report, and the CPU baseline (--no-extra / --no-roofline / --no-cpu-baseline still switch each of them off).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -175,6 +180,42 @@ def cpu_probe(threads, bg):
     print(json.dumps(dict(threads=threads, value=round(2 / el, 4), unit='images/s at batch 2', sample='1 timed iteration of the same Gmain+Dmain step at batch 2 after 1 warm-up')), flush=True)
 
 
+DUMP_SAMPLE = 1 << 20          # elements per sampled flat buffer (4 MB in float32); five of them + the small arrays stay far below 64 MB
+
+
+def dump_outputs(out_dir, pG, pD, ema, loss):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy in float32.  G's generated boxes and loss terms of
+    the step (loss.last: in graph mode the Gmain graph's own output buffers, rewritten by every replay), and the state the step leaves behind:
+    G's, D's and G_ema's parameters and G's and D's gradients of that step.  A flat buffer larger than DUMP_SAMPLE is sampled at fixed seeded
+    positions (the same positions for a module's parameters and gradients).  -> {name: shape}"""
+    import re
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if pG.fm.flat.is_cuda:          # (tensors on the host: no device runtime is touched)
+        torch.cuda.synchronize(pG.fm.flat.device)
+    arrays = {}
+    for k, v in sorted((loss.last or {}).items()):
+        if torch.is_tensor(v) and v.is_floating_point():
+            arrays['G_' + re.sub(r'[^A-Za-z0-9_.-]', '_', k)] = v
+    for name, fm, seed in (('G', pG.fm, 1), ('D', pD.fm, 2)):
+        idx = None
+        if fm.total > DUMP_SAMPLE:
+            idx = torch.randint(0, fm.total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values.to(fm.flat.device)
+        pick = (lambda t: t) if idx is None else (lambda t: t.index_select(0, idx))
+        arrays[f'{name}_params'] = pick(fm.flat)
+        arrays[f'{name}_grads'] = pick(fm.gflat)
+        if name == 'G':
+            arrays['G_ema_params'] = pick(ema.fm.flat)
+    shapes, total = {}, 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        shapes[name] = list(a.shape)
+    assert total <= 64 * 10 ** 6, f'--dump-outputs wrote {total} bytes'
+    return shapes
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cpu-probe-threads', type=int, default=0, help=argparse.SUPPRESS)
@@ -200,7 +241,15 @@ def parse_args():
                          "(training_loop.py:281-313: Gmain steps G only), so Gmain's D(fake) reads the evaluation Dmain differentiates; 'phase': once per phase; "
                          "--no-share-trunk: once per D pass, the reference's call pattern.  Same values in all three (parity-tested); the line reports all three rates")
     ap.add_argument('--no-overlap', action='store_true', help='N>1: exchange gradients after each backward graph instead of overlapping the all-reduce with it')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also measure the secondary configurations, the engine roofline and the CPU baseline (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="after the timed steps, write what the headline step computed in its last step as DIR/<name>.npy (float32): G's generated boxes and "
+                         "loss terms, and a fixed seeded sample of G's, D's and G_ema's parameters and of G's and D's gradients.  The last timed step then "
+                         "starts from the training state before the first step (restored outside the clock), so its inputs are the same in every run")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def _free_port():
@@ -279,7 +328,7 @@ def run(args, rank, local_rank, world):
     G = Generator(z_dim=4, f_dim=256, num_heads=4, num_layers=8, text_mode=args.text_mode, **kw).train().requires_grad_(False)
     D = Discriminator(f_dim=256, num_heads=4, num_layers=8, text_mode=args.text_mode, **kw).train().requires_grad_(False)
     G_sd_cpu = D_sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.text_mode == 'features':
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.text_mode == 'features':
         G_sd_cpu = {k: v.clone() for k, v in G.state_dict().items()}
         D_sd_cpu = {k: v.clone() for k, v in D.state_dict().items()}
     G_names = {n for n, _ in G.named_parameters()}
@@ -292,6 +341,20 @@ def run(args, rank, local_rank, world):
     ema = tl.EmaTracker(pG, G_ema)
     dp_world = tl.DataParallelStep(world_size=world)
     n_params = (pG.fm.total, pD.fm.total)
+    # --dump-outputs: the training state before the first step.  The weight gradients are summed with fp32 atomics (last-bit order effects) and
+    # training amplifies those bits from step to step (Adam turns a near-zero gradient's sign into a full lr step, saturated softmaxes follow),
+    # so after a few steps two runs hold different parameters.  The last timed step therefore starts from this state, restored outside the clock:
+    # its inputs are the same in every run and its outputs repeat to rounding.  (Counters and the in-graph RNG positions repeat anyway.)
+    init_state = None
+    if args.dump_outputs:
+        init_state = [(ph, ph.fm.flat.clone(), ph.m.clone(), ph.v.clone(), ph.step, ph.reg_steps) for ph in (pG, pD)] + [ema.fm.flat.clone()]
+
+    def restore_init_state():
+        for ph, flat, m, v, st, rst in init_state[:-1]:
+            ph.fm.flat.copy_(flat); ph.m.copy_(m); ph.v.copy_(v)
+            ph.step, ph.reg_steps, ph.reg_runs = st, rst, None
+        ema.fm.flat.copy_(init_state[-1])
+        tl.refresh_weight_planes(G); tl.refresh_weight_planes(D)   # the plane-format weight images follow the restored parameters
     torch.manual_seed(0 * world + rank)   # training_loop.py:101-102 seed rule
     side = torch.cuda.Stream()
     text_eval = [None]
@@ -301,8 +364,10 @@ def run(args, rank, local_rank, world):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(b_local, share, want_eager=False, local_only=False):
+    def measure(b_local, share, want_eager=False, local_only=False, dump=False):
         """W warm-up + K timed iterations at `b_local` samples per GPU; -> dict(value, ms_per_step, global_batch[, eager_step]).
+        dump (the headline): the last timed step starts from init_state (--dump-outputs), and rank 0 writes its outputs before any other measurement
+        steps the modules again.
         local_only (N > 1 diagnostics): the same step WITHOUT the gradient exchange (every rank steps on its own, as at N = 1): what the
         driver's N = 1 bench line measures, re-measured on this node's GPUs."""
         gb = b_local * world
@@ -339,12 +404,19 @@ def run(args, rank, local_rank, world):
         dp.record_exposed = world > 1 and not local_only
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        paused = 0.0
+        for i in range(args.steps):
+            if dump and init_state is not None and i == args.steps - 1:     # the dumped step starts from the state before the first step
+                barrier()
+                tp = time.perf_counter()
+                restore_init_state()
+                barrier()
+                paused = time.perf_counter() - tp
             step()
         torch.cuda.synchronize()
-        mine = time.perf_counter() - t0          # this rank's own clock, before the closing barrier
+        mine = time.perf_counter() - t0 - paused          # this rank's own clock, before the closing barrier
         barrier()
-        elapsed = time.perf_counter() - t0
+        elapsed = time.perf_counter() - t0 - paused
         dp.record_exposed = False
         diag = None
         if world > 1:
@@ -373,17 +445,19 @@ def run(args, rank, local_rank, world):
             out['diagnostics'] = diag
         if want_eager:
             out['eager_step'] = eager_step
+        if dump and rank == 0 and args.dump_outputs:
+            out['outputs'] = dump_outputs(args.dump_outputs, pG, pD, ema, loss)
         return out
 
     share = False if args.no_share_trunk else (True if args.share_trunk == 'phase' else 'iteration')
     extra = {}
     if args.per_gpu_batch:
-        primary, scaling = measure(args.per_gpu_batch, share, want_eager=True), 'weak'
+        primary, scaling = measure(args.per_gpu_batch, share, want_eager=True, dump=True), 'weak'
     else:
         gbatch = args.global_batch or 16
         assert gbatch % world == 0, f'global batch {gbatch} does not divide over {world} GPUs'
-        primary, scaling = measure(gbatch // world, share, want_eager=True), ('strong' if world > 1 else 'weak')
-        if not args.no_extra and not args.global_batch:
+        primary, scaling = measure(gbatch // world, share, want_eager=True, dump=True), ('strong' if world > 1 else 'weak')
+        if args.full and not args.no_extra and not args.global_batch:
             if world > 1:      # the same ranks at 16 samples per GPU (weak scaling: global batch 16 x N)
                 w = measure(16, share)
                 extra['weak_scaling'] = dict(value=w['value'], ms_per_step=w['ms_per_step'], global_batch=w['global_batch'], per_gpu_batch=16, unit='images/s',
@@ -440,7 +514,7 @@ def run(args, rank, local_rank, world):
     value, ms_per_step = primary['value'], primary['ms_per_step']
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # Dominant kernel = the f32-MFMA contraction engine (ldetr::gemm_f32_kernel<...>, every dense GEMM and implicit conv).
         # HIP events on the launch stream around each engine launch, algorithmic FLOPs = 2*M*N*K (GEMM) /
         # 2*pixels*Cout*KH*KW*Cin (conv fwd, bwd-data, bwd-weight alike), over 2 extra iterations.
@@ -632,14 +706,14 @@ def run(args, rank, local_rank, world):
                    scaling=scaling, vs_baseline=None, dtype='f32', data='synthetic',
                    config=dict(reference_call_pattern_images_s=extra.get('value_reference_call_pattern'), phase_trunk_sharing_images_s=extra.get('value_phase_trunk_sharing'),
                                headline_note="value = D's ResNet trunk evaluated once per iteration (value-identical: D's weights do not move between Gmain and Dmain); "
-                                             'quote it with phase_trunk_sharing_images_s (once per phase) and reference_call_pattern_images_s (once per D pass, as training/loss.py does)',
+                                             'quote it with phase_trunk_sharing_images_s (once per phase) and reference_call_pattern_images_s (once per D pass, as training/loss.py does), both measured by --full',
                                workload=f'BASELINE configs[{2 if world == 1 else 3}]: global batch {args.batch} ({b_local} per GPU), {bg}x{bg} backgrounds x 9 elements, full G+D adversarial '
                                         'step (Gmain+Dmain fwd/bwd, grad exchange + nan_to_num, Adam, EMA), train mode (dropout 0.1); ' +
                                         ('hot-path-only: frozen-BERT text features are an input, LM-decoder loss excluded' if args.text_mode == 'features' else f'text path on: {args.text_mode}, element texts of {args.text_valid} tokens padded to {args.text_tokens} as the reference tokenizer does; ' + (f'all {args.text_tokens} positions evaluated' if args.text_padded else f'the batch-longest text ({text_eval[0]} positions) evaluated: same values, parity-tested')),
                                parity_notes='values checked against oracle/ (pinned to the reference by tests/golden/*; the torchvision ResNet-50 body of the oracle is parity-UNPINNED: torchvision is '
                                             'absent from the build container, SURVEY 8c); dropout (on in this timed step, as in the reference) is validated statistically only; D-trunk sharing is value-identical '
                                             '(tests/test_model_gpu.py::test_iteration_level_D_trunk_sharing_matches_reference_call_pattern)',
-                               global_batch=args.batch, per_gpu_batch=b_local, background=bg, elements=9,
+                               global_batch=args.batch, per_gpu_batch=b_local, background=bg, elements=9, full=args.full, dumped_outputs=primary.get('outputs'),
                                parallelism=f'dp{world}', hip_graph=not args.no_graph, allreduce_overlapped_with_backward=(world > 1 and not args.no_graph and not args.no_overlap), text_mode=args.text_mode, text_tokens=(args.text_tokens if args.text_mode != 'features' else None), text_tokens_evaluated=text_eval[0], d_trunk_shared=False if args.no_share_trunk else args.share_trunk, params_G=n_params[0], params_D=n_params[1]),
                    roofline=roofline, cpu_baseline=cpu, **extra)
         print(json.dumps(out), flush=True)

@@ -222,7 +222,7 @@ def test_bench_two_ranks_on_one_gpu_prints_the_scaling_schema(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LDETR_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-roofline'], env=env, cwd=root,
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-roofline'], env=env, cwd=root,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -242,3 +242,41 @@ def test_bench_two_ranks_on_one_gpu_prints_the_scaling_schema(dev):
     assert d['single_gpu_reference']['per_gpu_batch'] == 16 and d['single_gpu_reference']['value_per_gpu'] > 0
     c = d['strong_scaling_ceiling']
     assert c['n_gpus'] == 2 and c['per_gpu_batch_share'] == 8 and 1.0 < c['value'] <= 2.05
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(dev, tmp_path):
+    """`python bench.py --gpus 1 --steps 4 --warmup 2 --dump-outputs DIR`: ONE JSON line with the headline fields and none of --full's
+    measurements, and DIR holds what the last timed step computed (G's boxes and loss terms, sampled parameters and gradients) as finite
+    float32 arrays, 64 MB at most.  Two runs write the same outputs up to rounding: the last timed step starts from the state before the first
+    step (the bar, 1e-3 of an array's largest value, is the run-to-run spread of one Dmain step that the fp32 gradient atomics leave: DESIGN.md)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--dump-outputs', str(tmp_path / tag)],
+                           cwd=root, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        runs.append(r)
+    out_dir = tmp_path / 'a'
+    for name in os.listdir(out_dir):
+        a, b = np.load(out_dir / name).astype(np.float64), np.load(tmp_path / 'b' / name).astype(np.float64)
+        err = np.abs(a - b).max() / (np.abs(b).max() + 1e-30) if a.size else 0.0
+        assert err <= 1e-3, f'{name}: two runs differ by {err:.2e} of the largest value'
+    r = runs[0]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, f'expected exactly one JSON line on stdout, got {len(lines)}'
+    d = json.loads(lines[0])
+    assert d['unit'] == 'images/s' and d['value'] > 0 and d['ms_per_step'] > 0 and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['steps'] == 4 and d['warmup'] == 2 and d['n_gpus'] == 1 and d['config']['full'] is False
+    assert d['roofline'] is None and d['cpu_baseline'] is None and 'value_reference_call_pattern' not in d and 'strong_scaling_ceiling' not in d
+    shapes = d['config']['dumped_outputs']
+    assert shapes['G_bbox_fake'] == [16, 9, 4] and {'G_params', 'G_grads', 'G_ema_params', 'D_params', 'D_grads'} <= set(shapes)
+    total = 0
+    for name, shape in shapes.items():
+        a = np.load(out_dir / f'{name}.npy')
+        assert a.dtype == np.float32 and list(a.shape) == shape and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6
+    assert np.abs(np.load(out_dir / 'D_grads.npy')).max() > 0, 'no gradient in the dumped step'

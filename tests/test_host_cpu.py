@@ -326,6 +326,35 @@ def test_bench_batch_helpers():
     assert not bt['padding_mask'].any()
 
 
+def test_bench_dump_outputs_float32_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output, G's boxes and loss terms from loss.last, flat buffers up to DUMP_SAMPLE elements
+    whole and larger ones at fixed seeded positions (the same for a module's parameters and gradients, the same in every run), within 64 MB."""
+    import types
+    import bench
+
+    def fm(n, seed):
+        g = torch.Generator().manual_seed(seed)
+        return types.SimpleNamespace(total=n, flat=torch.randn(n, generator=g), gflat=torch.randn(n, generator=g))
+    small, big = 1000, bench.DUMP_SAMPLE + 12345
+    pG, ema = types.SimpleNamespace(fm=fm(small, 1)), types.SimpleNamespace(fm=fm(small, 3))
+    pD = types.SimpleNamespace(fm=types.SimpleNamespace(total=big, flat=torch.arange(big, dtype=torch.float32), gflat=-torch.arange(big, dtype=torch.float32)))
+    loss = types.SimpleNamespace(last=dict(bbox_fake=torch.rand(2, 9, 4), loss_Ggen=torch.rand(2, 1, dtype=torch.float64), valid=torch.ones(2, dtype=torch.bool)))
+    shapes = bench.dump_outputs(str(tmp_path / 'a'), pG, pD, ema, loss)
+    assert shapes == {'G_bbox_fake': [2, 9, 4], 'G_loss_Ggen': [2, 1], 'G_params': [small], 'G_grads': [small], 'G_ema_params': [small],
+                      'D_params': [bench.DUMP_SAMPLE], 'D_grads': [bench.DUMP_SAMPLE]}
+    bench.dump_outputs(str(tmp_path / 'b'), pG, pD, ema, loss)
+    total = 0
+    for name in shapes:
+        a, b = np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy')
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6
+    assert np.array_equal(np.load(tmp_path / 'a' / 'G_params.npy'), pG.fm.flat.numpy())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'G_ema_params.npy'), ema.fm.flat.numpy())
+    dp, dg = np.load(tmp_path / 'a' / 'D_params.npy'), np.load(tmp_path / 'a' / 'D_grads.npy')
+    assert (np.diff(dp) >= 0).all() and np.unique(dp).size > bench.DUMP_SAMPLE // 2 and np.array_equal(dg, -dp)     # flat[i] = i, gflat[i] = -i
+
+
 def test_register_budgeted_kernels_use_no_scratch():
     """The contraction-engine / attention kernels are designed around their register budget; the build records clang's
     per-kernel resource usage and refuses scratch in them (guards against silent 10x regressions from an innocent edit)."""

@@ -361,7 +361,15 @@ def test_composition_loss_phases_vs_reference():
         want = {k[len(phase) + 8:]: v for k, v in d.items() if k.startswith(phase + '/report/')}
         assert set(want) == set(terms), set(want) ^ set(terms)
         for k, v in want.items():
-            close(terms[k], v, 2e-5)
+            # a term the reference's own fp32 run reproduces only to > 2e-5 of its fp64 value is ill-conditioned in fp32 (the alignment term:
+            # -log(1 - min |x_i - x_j|) of nearly equal coordinates), so its fp32 value depends on the host CPU's rounding: it is judged
+            # against the fp64 reference run instead, as close to it as the reference's own fp32 run is (x3, as the gradients below)
+            v64 = torch.as_tensor(d[f'{phase}/report64/{k}']).double()
+            e_ref = (torch.as_tensor(v).double() - v64).abs().max().item() / (v64.abs().max().item() + 1e-12)
+            if e_ref <= 2e-5:
+                close(terms[k], v, 2e-5)
+            else:
+                close(terms[k], v64, 3 * e_ref)
     gG['backbone.0.body.feats'] = fg.grad; gD['backbone.0.body.feats'] = fd.grad
     worst = ref_worst = 0.0
     for phase, grads in (('Gmain', gG), ('Dmain', gD)):

@@ -4,7 +4,7 @@
 tag=${1:-cfg5}; out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 ARGS="--bg 512 --per-gpu-batch 4 --text-mode encoder+lm"
-timeout 600 python bench.py $ARGS --steps 10 --warmup 3 --no-cpu-baseline > $out/cfg5_bench_line.json 2> $out/cfg5_bench.err
+timeout 600 python bench.py --full $ARGS --steps 10 --warmup 3 --no-cpu-baseline > $out/cfg5_bench_line.json 2> $out/cfg5_bench.err
 tail -c 400 $out/cfg5_bench.err
 cd /tmp; cd - > /dev/null
 rm -rf $out/prof

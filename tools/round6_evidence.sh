@@ -17,9 +17,9 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/pmc_step.py --aggregate /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE 2 > $out/pmc_traffic.json 2> $out/pmc_agg.err
 cp $out/pmc_traffic.json profiles/pmc_traffic.json       # the bench line below quotes it (same kernel sources: the digest is checked)
-LDETR_ENGINE_SHAPES=$out/engine_shapes.txt timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?"; cut -c1-300 $out/bench_line.json
+LDETR_ENGINE_SHAPES=$out/engine_shapes.txt timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?"; cut -c1-300 $out/bench_line.json
 rm -rf $out/prof
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python bench.py --no-cpu-baseline --no-extra > $out/prof_bench.json 2> $out/prof_bench.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python bench.py --full --no-cpu-baseline --no-extra > $out/prof_bench.json 2> $out/prof_bench.err
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats.csv
 rm -rf $out/prof
 for b in 16 2; do

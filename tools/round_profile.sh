@@ -9,9 +9,9 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log; tail -3 $out/pytest.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1; tail -1 $out/smoke.log
 fi
-timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?"; cut -c1-400 $out/bench_line.json
+timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?"; cut -c1-400 $out/bench_line.json
 rm -rf $out/prof
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python bench.py --no-cpu-baseline --no-extra > $out/prof_bench.json 2> $out/prof_bench.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python bench.py --full --no-cpu-baseline --no-extra > $out/prof_bench.json 2> $out/prof_bench.err
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats.csv
 rm -rf $out/prof
 for c in FETCH_SIZE WRITE_SIZE; do
