@@ -42,15 +42,16 @@ _legacy_warned = [False]
 
 
 def _warn_legacy_env():
-    """The development switches of rounds 1-4 were individual LDETR_* variables; since round 5 they are keys of LDETR_DEBUG="KEY=value,...".  A script that
-    still sets an old name would silently run the default path: say so once."""
+    """The development switches of rounds 1-4 were individual LDETR_* variables; since round 5 the ones that remain are keys of LDETR_DEBUG="KEY=value,...",
+    the others are retired.  A script that still sets an old name would silently run the default path: say so once."""
     if _legacy_warned[0]:
         return
     _legacy_warned[0] = True
     old = [k for k in _LEGACY_ENV if k in os.environ]
     if old:
         import warnings
-        warnings.warn(f'{", ".join(old)}: these switches are keys of LDETR_DEBUG now (e.g. LDETR_DEBUG="{old[0][6:]}=0") and are IGNORED as variables; see DESIGN.md, "Diagnostic switches"')
+        warnings.warn(f'{", ".join(old)}: these switch variables are IGNORED; the switches that remain are keys of LDETR_DEBUG="KEY=value,..."; see DESIGN.md, '
+                      '"Diagnostic switches"')
 
 
 def knob(key, default):

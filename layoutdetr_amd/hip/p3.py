@@ -138,12 +138,6 @@ def _epi(scale=None, shift=None, residual_p3=None, residual_f32=None, mask_p3=No
     return ep
 
 
-# Replay: while set (a list of precomputed outputs, in call order), _ConvP3Fn.forward takes its result from the list instead of launching --
-# the grouped forward of two trunks (conv_fwd_dual_raw, training/detr_backbone.py::dual_trunk_forward) computes both networks' activations in
-# shared launches first; each network's ordinary forward then only builds its autograd graph around them.
-_REPLAY = [None]
-
-
 def conv_fwd_dual_raw(x1, x2, wf1, wf2, wshape, ep1, ep2, stride, pad, out_f32):
     """ldetr_p3_conv2d_fwd_dual on two P3 inputs of the same shape -> (y1, y2); no autograd.  wf*: device addresses of the forward weight images."""
     N, H, W, I = p3_dims(x1)
@@ -168,7 +162,7 @@ class _ConvP3Fn(torch.autograd.Function):
     out_f32: the output leaves the P3 world (fp32 [N, OH, OW, O]); its incoming gradient is fp32 and the ReLU mask is applied here."""
 
     @staticmethod
-    def forward(ctx, x, weight, wfwd, wbwd, scale, shift, residual, stride, pad, relu, premasked, mask_input, passthru, out_f32):
+    def forward(ctx, x, weight, wfwd, wbwd, scale, shift, residual, stride, pad, relu, premasked, mask_input, passthru, out_f32, pre):
         core.require_gpu(x, weight)
         ctx.set_materialize_grads(False)
         N, H, W, I = p3_dims(x)
@@ -176,19 +170,19 @@ class _ConvP3Fn(torch.autograd.Function):
         OH = (H + 2 * pad - KH) // stride + 1
         OW = (W + 2 * pad - KW) // stride + 1
         x = x.contiguous()
-        res = residual.contiguous() if residual is not None else None
-        ep = _epi(scale, shift, residual_p3=res, relu=relu)
-        if _REPLAY[0] is not None:
-            y = _REPLAY[0].pop(0)          # computed by the grouped launch of dual_trunk_forward
-            if tuple(y.shape[:3]) != (N, OH, OW) or (y.dtype == torch.float32) != bool(out_f32):
-                raise RuntimeError('p3 replay: precomputed activation does not match this convolution')
-        elif out_f32:
-            y = torch.empty((N, OH, OW, O), device=x.device, dtype=torch.float32)
-            yp, yf = None, y
+        if pre is not None:
+            if tuple(pre.shape[:3]) != (N, OH, OW) or (pre.dtype == torch.float32) != bool(out_f32):
+                raise RuntimeError('p3 conv: the precomputed output does not match this convolution')
+            y = pre
         else:
-            y = p3_empty(N, OH, OW, O, x.device)
-            yp, yf = y, None
-        if _REPLAY[0] is None:
+            if out_f32:
+                y = torch.empty((N, OH, OW, O), device=x.device, dtype=torch.float32)
+                yp, yf = None, y
+            else:
+                y = p3_empty(N, OH, OW, O, x.device)
+                yp, yf = y, None
+            res = residual.contiguous() if residual is not None else None
+            ep = _epi(scale, shift, residual_p3=res, relu=relu)
             core.engine_call('ldetr_p3_conv2d_fwd', 2.0 * N * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_p3_conv2d_fwd(
                 core.ptr(x), N, H, W, I, ctypes.c_void_p(wfwd), O, KH, KW, stride, pad, ctypes.byref(ep), core.ptr(yp), core.ptr(yf), core.stream()), 'p3_conv2d_fwd'),
                 nbytes=6.0 * (x.numel() // 3 + weight.numel() + (res.numel() // 3 if res is not None else 0)) + (4.0 if out_f32 else 6.0) * N * OH * OW * O)
@@ -203,7 +197,7 @@ class _ConvP3Fn(torch.autograd.Function):
     def backward(ctx, dy, dx_pass=None):
         x, sc, ysave = ctx.saved_tensors
         if dy is None:
-            return (dx_pass,) + (None,) * 13
+            return (dx_pass,) + (None,) * 14
         stride, pad, relu, has_res, (N, H, W, I), (O, KH, KW, OH, OW), premasked, mask_input, out_f32, wbwd = ctx.cfg
         if out_f32:
             dy = core.f32c(dy)
@@ -235,7 +229,7 @@ class _ConvP3Fn(torch.autograd.Function):
                 core.ptr(dyp), N, OH, OW, O, ctypes.c_void_p(wbwd), core.ptr(x), I, KH, KW, stride, pad, H, W, ctypes.byref(ep), core.ptr(dx), None,
                 core.ptr(sc), core.ptr(dw_buf), None, core.stream()), 'p3_conv2d_bwd_pair'),
                 nbytes=6.0 * (dyp.numel() // 3 + wparam.numel() + 2 * N * H * W * I) + 6.0 * (x.numel() // 3) + 4.0 * wparam.numel())
-            return (dx, dw, None, None, None, None, dyp if need_res else None) + (None,) * 7
+            return (dx, dw, None, None, None, None, dyp if need_res else None) + (None,) * 8
         if need_x:
             dx = p3_empty(N, H, W, I, x.device)
             dxp = dx_pass.contiguous() if dx_pass is not None else None
@@ -259,10 +253,11 @@ class _ConvP3Fn(torch.autograd.Function):
                 nbytes=6.0 * (x.numel() // 3 + dyp.numel() // 3) + 4.0 * wparam.numel())
             dw = ret
         dres = dyp if need_res else None
-        return (dx, dw, None, None, None, None, dres) + (None,) * 7
+        return (dx, dw, None, None, None, None, dres) + (None,) * 8
 
 
 def conv2d_p3(x, weight, wptrs, scale=None, shift=None, residual=None, stride=1, pad=0, relu=False, premasked=False, mask_input=False,
-              passthru=False, out_f32=False):
-    """wptrs = (forward image, data-gradient image) device addresses from WeightPlanes.ptrs()."""
-    return _ConvP3Fn.apply(x, weight, wptrs[0], wptrs[1], scale, shift, residual, stride, pad, relu, premasked, mask_input, passthru, out_f32)
+              passthru=False, out_f32=False, pre=None):
+    """wptrs = (forward image, data-gradient image) device addresses from WeightPlanes.ptrs().  pre: this convolution's output, already computed
+    by a grouped launch (conv_fwd_dual_raw, training/detr_backbone.py::dual_trunk_forward): nothing is launched, only the autograd node is built."""
+    return _ConvP3Fn.apply(x, weight, wptrs[0], wptrs[1], scale, shift, residual, stride, pad, relu, premasked, mask_input, passthru, out_f32, pre)

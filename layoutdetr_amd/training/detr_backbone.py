@@ -106,19 +106,22 @@ class Bottleneck(nn.Module):
 
     p3_index = None   # (conv1, conv2, conv3, downsample or None): this block's rows in ResNet50Body's hip.p3.WeightPlanes
 
-    def forward_p3(self, x, planes, out_f32=False):
+    def forward_p3(self, x, planes, out_f32=False, pre=None):
         """The same block on P3 activations (hip/p3.py): x and the result are plane-format tensors; out_f32: the block output leaves the
-        trunk as fp32 [N, H, W, C] (its ReLU mask is then applied by this block's own backward)."""
+        trunk as fp32 [N, H, W, C] (its ReLU mask is then applied by this block's own backward).  pre: the block's (conv1, conv2, downsample or
+        None, conv3) outputs, already computed by dual_trunk_forward: the pass then only builds the autograd graph around them."""
+        p1, p2, pd, p3 = pre if pre is not None else (None,) * 4
         s1, b1 = self.bn1.folded(); s2, b2 = self.bn2.folded(); s3, b3 = self.bn3.folded()
         i1, i2, i3, idn = self.p3_index
-        out, x = hp3.conv2d_p3(x, self.conv1.weight, planes.ptrs(i1), s1, b1, None, 1, 0, relu=True, premasked=True, mask_input=self.mask_in, passthru=True)
-        out = hp3.conv2d_p3(out, self.conv2.weight, planes.ptrs(i2), s2, b2, None, self.conv2.stride, 1, relu=True, premasked=True, mask_input=True)
+        out, x = hp3.conv2d_p3(x, self.conv1.weight, planes.ptrs(i1), s1, b1, None, 1, 0, relu=True, premasked=True, mask_input=self.mask_in, passthru=True,
+                               pre=p1)
+        out = hp3.conv2d_p3(out, self.conv2.weight, planes.ptrs(i2), s2, b2, None, self.conv2.stride, 1, relu=True, premasked=True, mask_input=True, pre=p2)
         idt = x
         if self.downsample is not None:
             sd, bd = self.downsample[1].folded()
-            idt = hp3.conv2d_p3(x, self.downsample[0].weight, planes.ptrs(idn), sd, bd, None, self.downsample[0].stride, 0, relu=False)
+            idt = hp3.conv2d_p3(x, self.downsample[0].weight, planes.ptrs(idn), sd, bd, None, self.downsample[0].stride, 0, relu=False, pre=pd)
         return hp3.conv2d_p3(out, self.conv3.weight, planes.ptrs(i3), s3, b3, idt, 1, 0, relu=True, mask_input=True,
-                             premasked=self.premask_out and not out_f32, out_f32=out_f32)
+                             premasked=self.premask_out and not out_f32, out_f32=out_f32, pre=p3)
 
 
 class BackwardStages(object):
@@ -160,6 +163,12 @@ import weakref
 _P3_PLANES = weakref.WeakKeyDictionary()   # ResNet50Body -> hip.p3.WeightPlanes
 
 
+def trunk_body(module):
+    """The trunk body (backbone[0].body) of a Generator / Discriminator, else None."""
+    bb = getattr(module, 'backbone', None)
+    return bb[0].body if bb is not None and hasattr(bb[0], 'body') else None
+
+
 def existing_p3_planes(body):
     """The body's weight images if it ever took the plane-format path, else None (nothing is built here: 2 x 6 bytes per trunk weight)."""
     return _P3_PLANES.get(body)
@@ -181,10 +190,14 @@ class ResNet50Body(nn.Module):
             inplanes = planes * 4
             layers += [Bottleneck(inplanes, planes) for _ in range(1, blocks)]
             setattr(self, f'layer{li}', nn.Sequential(*layers))
-        blocks = [b for li in range(1, 5) for b in getattr(self, f'layer{li}')]
+        blocks = self.blocks()
         for prev, nxt in zip(blocks[:-1], blocks[1:]):     # every block output feeds exactly the next block
             prev.premask_out = True
             nxt.mask_in = True
+
+    def blocks(self):
+        """The 16 bottleneck blocks, layer1 .. layer4 in order."""
+        return [b for li in range(1, 5) for b in getattr(self, f'layer{li}')]
 
     def p3_planes(self):
         """P3 images of the 52 conv weights behind the stem (hip.p3.WeightPlanes; built on first use and kept OUTSIDE the module's state,
@@ -192,15 +205,14 @@ class ResNet50Body(nn.Module):
         planes = _P3_PLANES.get(self)
         if planes is None:
             convs = []
-            for li in range(1, 5):
-                for b in getattr(self, f'layer{li}'):
-                    i0 = len(convs)
-                    convs += [(b.conv1.weight, b.bn1), (b.conv2.weight, b.bn2), (b.conv3.weight, b.bn3)]
-                    idn = None
-                    if b.downsample is not None:
-                        idn = len(convs)
-                        convs.append((b.downsample[0].weight, b.downsample[1]))
-                    b.p3_index = (i0, i0 + 1, i0 + 2, idn)
+            for b in self.blocks():
+                i0 = len(convs)
+                convs += [(b.conv1.weight, b.bn1), (b.conv2.weight, b.bn2), (b.conv3.weight, b.bn3)]
+                idn = None
+                if b.downsample is not None:
+                    idn = len(convs)
+                    convs.append((b.downsample[0].weight, b.downsample[1]))
+                b.p3_index = (i0, i0 + 1, i0 + 2, idn)
             planes = _P3_PLANES[self] = hp3.WeightPlanes(convs)
         return planes
 
@@ -211,13 +223,7 @@ class ResNet50Body(nn.Module):
         N, H, W, C = x.shape
         return os.environ.get('LDETR_TRUNK_P3', '1') != '0' and N * H * W * 256 * 6 < 0x7fffffff and N * H * W < (1 << 24)
 
-    injected = None   # {(data_ptr, shape) of an input batch: its trunk output}, parked by dual_trunk_forward; consumed by the next forward on that batch
-
     def forward(self, x_nchw):
-        if self.injected:
-            hit = self.injected.pop((x_nchw.data_ptr(), tuple(x_nchw.shape)), None)
-            if hit is not None:
-                return hit
         x = self._entrance(x_nchw)
         if self.p3_enabled(x):
             return self._forward_p3(x)
@@ -237,74 +243,57 @@ class ResNet50Body(nn.Module):
         return hconv.maxpool3x3s2_nhwc(x)
 
     def _forward_p3(self, x, replay=None):
-        """replay: the plane-format input followed by the 52 convolutions' precomputed outputs in call order (dual_trunk_forward); the pass then only
-        builds the autograd graph."""
+        """replay: (the plane-format input, one (conv1, conv2, downsample or None, conv3) output tuple per block of blocks()), precomputed by
+        dual_trunk_forward; the pass then only builds the autograd graph around them."""
         planes = self.p3_planes()
         planes.ensure()
-        x = hp3.split(x, pre=(replay.pop(0) if replay is not None else None))
-        if replay is not None:
-            prev, hp3._REPLAY[0] = hp3._REPLAY[0], replay
-            try:
-                y = self._blocks_p3(x, planes)
-            finally:
-                hp3._REPLAY[0] = prev
-            if replay:
-                raise RuntimeError('p3 replay: precomputed activations left over')
-            return y
-        return self._blocks_p3(x, planes)
-
-    def _blocks_p3(self, x, planes):
-        for b in self.layer1:
-            x = b.forward_p3(x, planes)
-        for b in self.layer2:
-            x = b.forward_p3(x, planes)
-        st = self.stages if (self.stages is not None and x.requires_grad and torch.is_grad_enabled()) else None
-        if st is not None:
-            x = st.cut(x, 3)
-        for b in self.layer3:
-            x = b.forward_p3(x, planes)
-        n4 = len(self.layer4)
-        for i, b in enumerate(self.layer4):
-            x = b.forward_p3(x, planes, out_f32=(i == n4 - 1))
+        split, pre = replay if replay is not None else (None, None)
+        x = hp3.split(x, pre=split)
+        blocks = self.blocks()
+        st = None
+        for i, b in enumerate(blocks):
+            if b is self.layer3[0]:        # backward stage boundary layer1-2 | layer3-4
+                st = self.stages if (self.stages is not None and x.requires_grad and torch.is_grad_enabled()) else None
+                if st is not None:
+                    x = st.cut(x, 3)
+            x = b.forward_p3(x, planes, out_f32=(i == len(blocks) - 1), pre=None if pre is None else pre[i])
         if st is not None:
             x = st.cut(x, 2)
         return x  # fp32 [N, H/32, W/32, 2048]
 
 
 def dual_trunk_forward(body_a, body_b, x_a, x_b):
-    """body_a(x_a), body_b(x_b) for two ResNet50Body modules on same-shaped image batches, every plane-format convolution of the two trunks as ONE
-    grouped launch (ldetr_p3_conv2d_fwd_dual).  G's and D's trunks convolve the same backgrounds through the same architecture with different
-    weights (networks_detr.py:79-82 and :230-233 build one backbone each); each conv alone is a short launch whose blocks run in lock-step, and two
-    of them in one grid overlap each other's fill and store burst.  Values are those of the two separate forwards bit for bit (same
-    kernels, same tiles); each module's autograd graph is built by its own ordinary forward, replayed around the precomputed activations, so the
-    two backward passes stay independent (they run in different phases)."""
+    """(body_a(x_a), body_b(x_b)) for two ResNet50Body modules on same-shaped image batches, every plane-format convolution of the two trunks as ONE
+    grouped launch (ldetr_p3_conv2d_fwd_dual); None if the plane-format engine does not take them (p3_enabled on the stems' output, or different
+    shapes).  G's and D's trunks convolve the same backgrounds through the same architecture with different weights (networks_detr.py:79-82 and
+    :230-233 build one backbone each); each conv alone is a short launch whose blocks run in lock-step, and two of them in one grid overlap each
+    other's fill and store burst (DESIGN 4.0).  Values are those of the two separate forwards bit for bit (same kernels, same tiles); each module's
+    autograd graph is built by its own ordinary forward, replayed around the precomputed activations, so the two backward passes stay independent
+    (they run in different phases)."""
     ea, eb = body_a._entrance(x_a), body_b._entrance(x_b)
     if not (body_a.p3_enabled(ea) and tuple(ea.shape) == tuple(eb.shape)):
-        return body_a(x_a), body_b(x_b)
+        return None
     planes_a, planes_b = body_a.p3_planes(), body_b.p3_planes()
     planes_a.ensure(); planes_b.ensure()
-    outs_a, outs_b = [], []
     with torch.no_grad():
         ca, cb = hp3.split_raw(ea.detach()), hp3.split_raw(eb.detach())
-        outs_a.append(ca); outs_b.append(cb)
-        blocks_a = [b for li in range(1, 5) for b in getattr(body_a, f'layer{li}')]
-        blocks_b = [b for li in range(1, 5) for b in getattr(body_b, f'layer{li}')]
+        replay_a, replay_b = (ca, []), (cb, [])
 
         def dual(xa, xb, conv_a, conv_b, ia, ib, bn_a, bn_b, stride, pad, relu, res_a=None, res_b=None, out_f32=False):
             (sa, ha), (sb, hb) = bn_a.folded(), bn_b.folded()
-            ya, yb = hp3.conv_fwd_dual_raw(xa, xb, planes_a.ptrs(ia)[0], planes_b.ptrs(ib)[0], conv_a.weight.shape, hp3._epi(sa, ha, residual_p3=res_a, relu=relu),
-                                           hp3._epi(sb, hb, residual_p3=res_b, relu=relu), stride, pad, out_f32)
-            outs_a.append(ya); outs_b.append(yb)
-            return ya, yb
+            return hp3.conv_fwd_dual_raw(xa, xb, planes_a.ptrs(ia)[0], planes_b.ptrs(ib)[0], conv_a.weight.shape, hp3._epi(sa, ha, residual_p3=res_a, relu=relu),
+                                         hp3._epi(sb, hb, residual_p3=res_b, relu=relu), stride, pad, out_f32)
+        blocks_a, blocks_b = body_a.blocks(), body_b.blocks()
         for i, (ba, bb) in enumerate(zip(blocks_a, blocks_b)):
             (a1, a2, a3, ad), (b1, b2, b3, bd) = ba.p3_index, bb.p3_index
             o1a, o1b = dual(ca, cb, ba.conv1, bb.conv1, a1, b1, ba.bn1, bb.bn1, 1, 0, True)
             o2a, o2b = dual(o1a, o1b, ba.conv2, bb.conv2, a2, b2, ba.bn2, bb.bn2, ba.conv2.stride, 1, True)
-            ida, idb = ca, cb
+            ida, idb, oda, odb = ca, cb, None, None
             if ba.downsample is not None:
-                ida, idb = dual(ca, cb, ba.downsample[0], bb.downsample[0], ad, bd, ba.downsample[1], bb.downsample[1], ba.downsample[0].stride, 0, False)
+                ida, idb = oda, odb = dual(ca, cb, ba.downsample[0], bb.downsample[0], ad, bd, ba.downsample[1], bb.downsample[1], ba.downsample[0].stride, 0, False)
             ca, cb = dual(o2a, o2b, ba.conv3, bb.conv3, a3, b3, ba.bn3, bb.bn3, 1, 0, True, ida, idb, out_f32=(i == len(blocks_a) - 1))
-    return body_a._forward_p3(ea, replay=outs_a), body_b._forward_p3(eb, replay=outs_b)
+            replay_a[1].append((o1a, o2a, oda, ca)); replay_b[1].append((o1b, o2b, odb, cb))
+    return body_a._forward_p3(ea, replay=replay_a), body_b._forward_p3(eb, replay=replay_b)
 
 
 class BackboneBase(nn.Module):
@@ -318,9 +307,13 @@ class BackboneBase(nn.Module):
         self.body = backbone
         self.num_channels = num_channels
 
-    def forward(self, tensor_list):
-        if isinstance(tensor_list, NestedTensor):
-            x = self.body(tensor_list.tensors).permute(0, 3, 1, 2)  # NCHW-shaped view of NHWC memory
+    def forward(self, tensor_list, body_out=None):
+        """body_out: the body's output on these images, already computed (dual_trunk_forward)."""
+        nested = isinstance(tensor_list, NestedTensor)
+        if body_out is None:
+            body_out = self.body(tensor_list.tensors if nested else tensor_list)
+        x = body_out.permute(0, 3, 1, 2)  # NCHW-shaped view of NHWC memory
+        if nested:
             m = tensor_list.mask
             assert m is not None
             if getattr(tensor_list, 'uniform', False):
@@ -328,7 +321,7 @@ class BackboneBase(nn.Module):
             else:
                 mask = F.interpolate(m[None].float(), size=x.shape[-2:]).to(torch.bool)[0]
             return OrderedDict([('0', NestedTensor(x, mask, getattr(tensor_list, 'uniform', False)))])
-        return OrderedDict([('0', self.body(tensor_list).permute(0, 3, 1, 2))])
+        return OrderedDict([('0', x)])
 
 
 class Backbone(BackboneBase):
@@ -344,12 +337,12 @@ class Joiner(nn.Sequential):
     def __init__(self, backbone, position_embedding):
         super().__init__(backbone, position_embedding)
 
-    def forward(self, tensor_list):
+    def forward(self, tensor_list, body_out=None):
         if isinstance(tensor_list, NestedTensor):
-            xs = self[0](tensor_list)
+            xs = self[0](tensor_list, body_out)
             out, pos = [], []
             for _, x in xs.items():
                 out.append(x)
                 pos.append(self[1](x).to(x.tensors.dtype))
             return out, pos
-        return list(self[0](tensor_list).values())
+        return list(self[0](tensor_list, body_out).values())

@@ -8,10 +8,12 @@ twice-differentiable nodes of hip/composite.py (SURVEY §7 'second-order autogra
 import torch
 import torch.nn.functional as F
 
+from ..detr_util.misc import NestedTensor
 from ..hip import composite, core
 
 from ..hip import losses as hl
-from ..metrics.metric_layoutnet import compute_alignment, compute_overlap, generalized_iou_loss, layout_losses_fused, layout_losses_per_sample
+from ..metrics.metric_layoutnet import compute_alignment, compute_overlap, generalized_iou_loss, layout_losses_per_sample
+from .detr_backbone import ResNet50Body, dual_trunk_forward, trunk_body
 
 
 def _masked_mse(a, b, valid):
@@ -22,17 +24,12 @@ def _masked_mse(a, b, valid):
     return ((a - b).square().sum(-1) * vf).sum() / (vf.sum().clamp_min(1.0) * a.shape[-1])
 
 
-def _masked_ce(logits, target, valid, raw=False):
-    """F.cross_entropy(logits[valid], target[valid]) without the gather: logits [B,N,L].  On the GPU the padded slots become ignored
-    targets of the fused softmax-cross-entropy kernel (csrc/xent.hip: loss and row log-sum-exp in one pass, gradient in one pass):
-    the same mean over the same slots in 4 launches instead of ~13.  raw: the (loss sum, count) pair for hip.losses.combine's RATIO term."""
-    if logits.is_cuda and logits.dtype == torch.float32:
-        from .med import softmax_cross_entropy
-        return softmax_cross_entropy(logits.flatten(0, 1), target.flatten().masked_fill(~valid.flatten(), -100), raw=raw)
-    assert not raw
-    vf = valid.to(logits.dtype).flatten()
-    ce = F.cross_entropy(logits.flatten(0, 1), target.flatten(), reduction='none')
-    return (ce * vf).sum() / vf.sum().clamp_min(1.0)
+def _masked_ce(logits, target, valid):
+    """F.cross_entropy(logits[valid], target[valid]) without the gather, as the (loss sum, count) pair of hip.losses.combine's RATIO term:
+    logits [B,N,L]; the padded slots become ignored targets of the fused softmax-cross-entropy kernel (csrc/xent.hip: loss and row log-sum-exp
+    in one pass, gradient in one pass): the same mean over the same slots in 4 launches instead of ~13."""
+    from .med import softmax_cross_entropy
+    return softmax_cross_entropy(logits.flatten(0, 1), target.flatten().masked_fill(~valid.flatten(), -100), raw=True)
 
 
 def _masked_giou(a, b, valid):
@@ -54,8 +51,15 @@ def _masked_giou(a, b, valid):
     return (per * vf).sum() / vf.sum().clamp_min(1.0)
 
 
+def _detached(trunk_out):
+    """A trunk output (Generator / Discriminator `trunk_out`) without its autograd graph."""
+    feats, pos = trunk_out
+    return [NestedTensor(f.tensors.detach(), f.mask, getattr(f, 'uniform', False)) for f in feats], [p.detach() for p in pos]
+
+
 class Loss:
-    def accumulate_gradients(self, phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, cur_nimg):
+    def accumulate_gradients(self, phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, cur_nimg,
+                             trunks=None):
         raise NotImplementedError()
 
 
@@ -89,36 +93,26 @@ class StyleGAN2Loss(Loss):
         # gradient (the reference recomputes it, training/loss.py:176-210: two run_D calls, two backward calls).  Same losses and
         # gradients up to fp32 summation order; share_D_trunk=False restores the reference's call pattern.
         self.share_D_trunk = share_D_trunk
-        # with a shared trunk, D(fake) and D(real) of Dmain also run as one batch of 2B (values identical; LDETR_DEBUG="PAIR_D=0" = two calls)
-        self.pair_D_passes = bool(share_D_trunk) and core.knob('PAIR_D', 1) != 0
-        self.fused_layout_losses = True   # csrc/layout_loss.hip (static-shape path)
-        self.fused_loss_tail = core.knob('FUSED_LOSS_TAIL', 1) != 0           # hip.losses.combine: a phase's tail as one launch per direction
+        # with a shared trunk, D(fake) and D(real) of Dmain also run as one batch of 2B (values identical)
+        self.pair_D_passes = bool(share_D_trunk) and hasattr(D, 'forward_pair')
         # share_D_trunk='iteration' goes one step further: D's weights do not change between the Gmain and the Dmain phase of one
         # iteration (Gmain updates G only, training_loop.py:281-313), so ONE trunk evaluation per iteration serves D(fake) in Gmain
-        # (values only: D is frozen there) and both D passes of Dmain (with its autograd graph).  The iteration driver calls
-        # precompute_D_trunk() before the phases; without that call the per-phase behaviour above applies.
-        self._trunk_cache = {}
+        # (values only: D is frozen there) and both D passes of Dmain (with its autograd graph).  The iteration driver gets it from
+        # precompute_D_trunk() before the phases and hands it to them (accumulate_gradients(trunks=)); without it the per-phase behaviour
+        # above applies.
         self._reporting = report_fn is not None   # the sign() statistics cost a launch each: only formed when someone listens
         self.report = report_fn if report_fn is not None else (lambda name, value: None)
         self.last = {}
 
-    @staticmethod
-    def _bg_key(background):
-        return (background.data_ptr(), tuple(background.shape)) if isinstance(background, torch.Tensor) else id(background)
-
     def precompute_D_trunk(self, background, stages=None):
-        """Evaluate D's trunk on `background` with gradient tracking and park it for this iteration's phases.
-        stages: a detr_backbone.BackwardStages that records the trunk's backward cuts (Dmain's staged backward continues from them)."""
+        """share_D_trunk='iteration': D's trunk on `background` with gradient tracking, evaluated once for this iteration's phases, and G's trunk
+        for the Gmain phase beside it (grouped_trunks) -> (G's trunk output or None, D's): what accumulate_gradients(trunks=) takes.  None in the
+        other share modes.  stages: a detr_backbone.BackwardStages that records D's trunk cuts (Dmain's staged backward continues from them); G's
+        trunk is then left to Gmain."""
         if self.share_D_trunk != 'iteration' or not hasattr(self.D, 'trunk'):
-            return
+            return None
         body = self.D.backbone[0].body
-        # G's trunk for the Gmain phase rides along: same backgrounds, same architecture, different weights -> every convolution of the two trunks
-        # as one grouped launch (detr_backbone.dual_trunk_forward); G's output is parked on its body and consumed by Gmain's generator forward.
-        # Not with a staged backward (its cuts are recorded inside the ordinary forward) and not for ragged backgrounds.
-        g_body = self.G.backbone[0].body if hasattr(self.G, 'backbone') else None
-        dual = (stages is None and g_body is not None and isinstance(background, torch.Tensor) and core.knob('DUAL_TRUNK', 1) != 0
-                and type(g_body) is type(body) and hasattr(body, '_entrance'))
-        trunk_params = list(self.D.backbone.parameters()) + (list(self.G.backbone.parameters()) if dual else [])
+        trunk_params = [p for m in (self.G, self.D) if hasattr(m, 'backbone') for p in m.backbone.parameters()]
         was = [p.requires_grad for p in trunk_params]
         for p in trunk_params:
             p.requires_grad_(True)     # the autograd graphs are built now, used by the phases' backward passes (training_loop.py:282 sets it there)
@@ -126,53 +120,33 @@ class StyleGAN2Loss(Loss):
             if stages is not None:
                 body.stages = stages
             with torch.enable_grad():
-                if dual:
-                    from .detr_backbone import dual_trunk_forward
-                    key = (background.data_ptr(), tuple(background.shape))
-                    out_g, out_d = dual_trunk_forward(g_body, body, background, background)
-                    g_body.injected = dict(g_body.injected or {}); g_body.injected[key] = out_g
-                    body.injected = {key: out_d}
-                self._trunk_cache[self._bg_key(background)] = self.D.trunk(background)
+                g_out, d_out = self.grouped_trunks(background)
+                return g_out, (d_out if d_out is not None else self.D.trunk(background))
         finally:
             if stages is not None:
                 body.stages = None
-            body.injected = None
             for p, w in zip(trunk_params, was):
                 p.requires_grad_(w)
 
-    def _cached_trunk(self, background, detach, pop):
-        key = self._bg_key(background)
-        out = self._trunk_cache.pop(key, None) if pop else self._trunk_cache.get(key)
-        if out is None or not detach:
-            return out
-        from ..detr_util.misc import NestedTensor
-        feats, pos = out
-        return [NestedTensor(f.tensors.detach(), f.mask, getattr(f, 'uniform', False)) for f in feats], [p.detach() for p in pos]
+    def grouped_trunks(self, background):
+        """(G's, D's) trunk output on `background` (networks_detr `trunk_out`), every plane-format convolution of the two trunks as one grouped launch
+        (detr_backbone.dual_trunk_forward); each module's autograd graph is built by its own replayed forward, so a frozen module gets none.
+        (None, None) where grouping does not apply -- ragged backgrounds, a staged backward's cuts, the trunk off the plane-format engine --: each
+        forward then evaluates its own trunk."""
+        g_body, d_body = trunk_body(self.G), trunk_body(self.D)
+        if (not isinstance(background, torch.Tensor) or not isinstance(g_body, ResNet50Body) or type(d_body) is not type(g_body)
+                or g_body.stages is not None or d_body.stages is not None):
+            return None, None
+        outs = dual_trunk_forward(g_body, d_body, background, background)
+        if outs is None:
+            return None, None
+        return self.G.trunk(background, body_out=outs[0]), self.D.trunk(background, body_out=outs[1])
 
-    def _dual_trunks(self, background):
-        """G's and D's trunk on `background` as grouped launches (detr_backbone.dual_trunk_forward), parked on the two bodies for the G and D forwards
-        that follow in this call.  Used where a phase evaluates both trunks itself (the reference's call pattern and phase-level sharing: Gmain's
-        G + D(fake), Dmain's G + first D pass); each module's graph is built by its own replayed forward, so a frozen module gets none."""
-        if core.knob('DUAL_TRUNK', 1) == 0 or not isinstance(background, torch.Tensor) or not hasattr(self.G, 'backbone') or not hasattr(self.D, 'backbone'):
-            return
-        g_body, d_body = self.G.backbone[0].body, self.D.backbone[0].body
-        if type(g_body) is not type(d_body) or not hasattr(g_body, '_entrance') or g_body.stages is not None or d_body.stages is not None:
-            return
-        from .detr_backbone import dual_trunk_forward
-        key = (background.data_ptr(), tuple(background.shape))
-        out_g, out_d = dual_trunk_forward(g_body, d_body, background, background)
-        g_body.injected = {key: out_g}
-        d_body.injected = {key: out_d}
-
-    def _drop_parked_trunks(self):
-        for m in (self.G, self.D):
-            if hasattr(m, 'backbone') and getattr(m.backbone[0].body, 'injected', None):
-                m.backbone[0].body.injected = None
-
-    def run_G(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, update_emas=False):
+    def run_G(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, update_emas=False, trunk_out=None):
+        kw = {} if trunk_out is None else dict(trunk_out=trunk_out)
         if not reconst:
-            return self.G(z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c)
-        return self.G(z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst)
+            return self.G(z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, **kw)
+        return self.G(z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst, **kw)
 
     def run_D(self, bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, blur_sigma=0, update_emas=False,
               trunk_out=None):
@@ -181,26 +155,21 @@ class StyleGAN2Loss(Loss):
             return self.D(bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, **kw)
         return self.D(bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, reconst, **kw)
 
-    def g_main_loss(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=1.0):
+    def g_main_loss(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=1.0, trunks=None):
+        """trunks: (G's, D's) trunk output of precompute_D_trunk; D's is read without its graph (D is frozen in this phase).  None: both trunks are
+        evaluated here, grouped."""
         w = self.w
         valid = ~padding_mask
         static = bool(getattr(self.G, 'static_shapes', False))
-        cached = self._cached_trunk(background, detach=True, pop=False)
-        if cached is None:
-            self._dual_trunks(background)      # G's trunk and the trunk of D(fake) in one pass
-        bbox_fake, loss_z, cls_logits, loss_lm, loss_text_len = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c, reconst=True)
-        gen_logits, gen_logits_uncond = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c,
-                                                   trunk_out=cached)
+        g_trunk, d_trunk = self.grouped_trunks(background) if trunks is None else (trunks[0], _detached(trunks[1]))
+        bbox_fake, loss_z, cls_logits, loss_lm, loss_text_len = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c,
+                                                                           reconst=True, trunk_out=g_trunk)
+        gen_logits, gen_logits_uncond = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c, trunk_out=d_trunk)
         T = hl.Term
-        w_ = lambda v, key: v * w[key]      # noqa: E731
-        fused_tail = self.fused_loss_tail and gen_logits.is_cuda
         lay = None
-        if static and self.fused_layout_losses and bbox_fake.is_cuda and bbox_fake.shape[1] <= 64:
+        if static and bbox_fake.is_cuda and bbox_fake.shape[1] <= 64:
             # one launch for the four layout terms and their gradients (csrc/layout_loss.hip) instead of ~280 elementwise ones
-            if fused_tail:
-                lay = layout_losses_per_sample(bbox_fake, bbox_real, valid)
-            else:
-                l_rec, l_giou, l_ovl, l_aln = layout_losses_fused(bbox_fake, bbox_real, valid)
+            lay = layout_losses_per_sample(bbox_fake, bbox_real, valid)
         elif static:
             l_rec, l_giou = _masked_mse(bbox_fake, bbox_real, valid), _masked_giou(bbox_fake, bbox_real, valid)
             l_ovl, l_aln = compute_overlap(bbox_fake, valid), compute_alignment(bbox_fake, valid)
@@ -210,49 +179,40 @@ class StyleGAN2Loss(Loss):
         self.report('Loss/scores/fake', gen_logits)
         if self._reporting:
             self.report('Loss/signs/fake', gen_logits.sign())
-        if fused_tail:
-            # the whole tail -- softplus of the two scores, the weights, the sum over the terms, the batch mean and the gain -- and its backward as one
-            # launch per direction (hip.losses.combine) instead of ~30 + ~40 scalar-sized ATen launches
-            terms = [T('loss_Ggen', gen_logits, 1.0, hl.SOFTPLUS_NEG), T('loss_Ggen_uncond', gen_logits_uncond, 1.0, hl.SOFTPLUS_NEG)]
-            if lay is not None:
-                terms.append(T(['loss_Ggen_bbox_rec', 'loss_Ggen_bbox_gIoU', 'loss_Ggen_overlapping', 'loss_Ggen_alignment'], lay,
-                               [w['Ggen_bbox_rec'], w['Ggen_bbox_gIoU'], w['Ggen_overlapping'], w['Ggen_alignment']], hl.IDENT, [True, True, False, False]))
-            else:
-                terms += [T('loss_Ggen_bbox_rec', l_rec, w['Ggen_bbox_rec']), T('loss_Ggen_bbox_gIoU', l_giou, w['Ggen_bbox_gIoU']),
-                          T('loss_Ggen_overlapping', l_ovl, w['Ggen_overlapping']), T('loss_Ggen_alignment', l_aln, w['Ggen_alignment'])]
-            terms.append(T('loss_Ggen_z_rec', loss_z, w['Ggen_z_rec']))
-            if static:
-                terms.append(T('loss_Ggen_bbox_cls', _masked_ce(cls_logits, bbox_class, valid, raw=True), w['Ggen_bbox_cls'], hl.RATIO))
-            else:
-                terms.append(T('loss_Ggen_bbox_cls', F.cross_entropy(cls_logits, bbox_class[valid]), w['Ggen_bbox_cls']))
-            terms += [T('loss_Ggen_text_rec', loss_lm, w['Ggen_text_rec']), T('loss_Ggen_text_len_rec', loss_text_len, w['Ggen_text_len_rec'])]
-            total, rep = hl.combine(terms, gain)
-            for k, v in rep.items():
-                self.report('Loss/G/' + k, v)
-            self.last = dict(bbox_fake=bbox_fake.detach(), **{k: v.detach() for k, v in rep.items()})
-            return total
-        terms = dict(
-            loss_Ggen=F.softplus(-gen_logits),
-            loss_Ggen_uncond=F.softplus(-gen_logits_uncond),
-            loss_Ggen_bbox_rec=w_(l_rec, 'Ggen_bbox_rec'),
-            loss_Ggen_bbox_gIoU=w_(l_giou, 'Ggen_bbox_gIoU'),
-            loss_Ggen_overlapping=w_(l_ovl, 'Ggen_overlapping'),
-            loss_Ggen_alignment=w_(l_aln, 'Ggen_alignment'),
-            loss_Ggen_z_rec=w_(loss_z, 'Ggen_z_rec'),
-            loss_Ggen_bbox_cls=w_(_masked_ce(cls_logits, bbox_class, valid) if static else F.cross_entropy(cls_logits, bbox_class[valid]), 'Ggen_bbox_cls'),
-            loss_Ggen_text_rec=w_(loss_lm, 'Ggen_text_rec'),
-            loss_Ggen_text_len_rec=w_(loss_text_len, 'Ggen_text_len_rec'),
-        )
-        for k, v in terms.items():
+        # the whole tail -- softplus of the two scores, the weights, the sum over the terms, the batch mean and the gain -- and its backward as one
+        # launch per direction (hip.losses.combine) instead of ~30 + ~40 scalar-sized ATen launches
+        terms = [T('loss_Ggen', gen_logits, 1.0, hl.SOFTPLUS_NEG), T('loss_Ggen_uncond', gen_logits_uncond, 1.0, hl.SOFTPLUS_NEG)]
+        if lay is not None:
+            terms.append(T(['loss_Ggen_bbox_rec', 'loss_Ggen_bbox_gIoU', 'loss_Ggen_overlapping', 'loss_Ggen_alignment'], lay,
+                           [w['Ggen_bbox_rec'], w['Ggen_bbox_gIoU'], w['Ggen_overlapping'], w['Ggen_alignment']], hl.IDENT, [True, True, False, False]))
+        else:
+            terms += [T('loss_Ggen_bbox_rec', l_rec, w['Ggen_bbox_rec']), T('loss_Ggen_bbox_gIoU', l_giou, w['Ggen_bbox_gIoU']),
+                      T('loss_Ggen_overlapping', l_ovl, w['Ggen_overlapping']), T('loss_Ggen_alignment', l_aln, w['Ggen_alignment'])]
+        terms.append(T('loss_Ggen_z_rec', loss_z, w['Ggen_z_rec']))
+        if static:
+            terms.append(T('loss_Ggen_bbox_cls', _masked_ce(cls_logits, bbox_class, valid), w['Ggen_bbox_cls'], hl.RATIO))
+        else:
+            terms.append(T('loss_Ggen_bbox_cls', F.cross_entropy(cls_logits, bbox_class[valid]), w['Ggen_bbox_cls']))
+        terms += [T('loss_Ggen_text_rec', loss_lm, w['Ggen_text_rec']), T('loss_Ggen_text_len_rec', loss_text_len, w['Ggen_text_len_rec'])]
+        total, rep = hl.combine(terms, gain)
+        for k, v in rep.items():
             self.report('Loss/G/' + k, v)
-        total = sum(terms.values())
-        self.last = dict(bbox_fake=bbox_fake.detach(), **{k: v.detach() for k, v in terms.items()})
-        return total.mean().mul(gain)
+        self.last = dict(bbox_fake=bbox_fake.detach(), **{k: v.detach() for k, v in rep.items()})
+        return total
+
+    def _generate_for_D(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=None):
+        """G's layouts for a D phase (loss.py:146-149) and D's trunk output on the backgrounds: `trunk_out` if given, else evaluated here grouped with
+        G's trunk (grouped_trunks; None where that does not apply: D then evaluates its own) -> (bbox_fake, D's trunk_out)."""
+        g_trunk = None
+        if trunk_out is None:
+            g_trunk, trunk_out = self.grouped_trunks(background)
+        bbox_fake = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True, trunk_out=g_trunk)
+        return bbox_fake, trunk_out
 
     def d_gen_terms(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=None, gen_out=None):
         """-> the terms of loss.py:146-160 (D on the generated layout) as hip.losses.Term objects."""
         if gen_out is None:
-            bbox_fake = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True)
+            bbox_fake, trunk_out = self._generate_for_D(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out)
             gen_out = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True, trunk_out=trunk_out)
         gen_logits, gen_logits_uncond = gen_out
         self.report('Loss/scores/fake', gen_logits)
@@ -270,12 +230,11 @@ class StyleGAN2Loss(Loss):
             real_out = self.run_D(bbox_real_tmp, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, reconst=True, trunk_out=trunk_out)
         (real_logits, real_logits_uncond, bbox_rec, cls_logits, loss_lm, loss_text_len, bg_rec, bbox_rec_uncond, cls_logits_uncond) = real_out
         T = hl.Term
-        fused = self.fused_loss_tail and real_logits.is_cuda and static
 
         def ce(logits):
-            if fused:
-                return dict(x=_masked_ce(logits, bbox_class, valid, raw=True), fn=hl.RATIO)
-            return dict(x=_masked_ce(logits, bbox_class, valid) if static else F.cross_entropy(logits, bbox_class[valid]))
+            if static:
+                return dict(x=_masked_ce(logits, bbox_class, valid), fn=hl.RATIO)
+            return dict(x=F.cross_entropy(logits, bbox_class[valid]))
         mse = (lambda a: _masked_mse(a, bbox_real_tmp, valid)) if static else (lambda a: F.mse_loss(a, bbox_real_tmp[valid]))
         self.report('Loss/scores/real', real_logits)
         if self._reporting:
@@ -288,14 +247,9 @@ class StyleGAN2Loss(Loss):
                 T('loss_Dreal_bbox_cls_uncond', weight=w['Dreal_bbox_cls'], **ce(cls_logits_uncond))]
 
     def _finish(self, terms, prefix, gain=1.0):
-        """sum of the terms -> batch mean -> x gain (loss.py:213, 253 + the .mul(gain) of :116, 160, 218), every term reported like the reference does.
-        On the GPU one launch per direction for all of it (hip.losses.combine)."""
-        if self.fused_loss_tail and terms[0].x.is_cuda:
-            total, rep = hl.combine(terms, gain)
-        else:
-            f = {hl.IDENT: lambda x: x, hl.SOFTPLUS: F.softplus, hl.SOFTPLUS_NEG: lambda x: F.softplus(-x)}
-            rep = {t.name: f[t.fn](t.x) * t.weight for t in terms}
-            total = sum(rep.values()).mean().mul(gain)
+        """sum of the terms -> batch mean -> x gain (loss.py:213, 253 + the .mul(gain) of :116, 160, 218), every term reported like the reference does:
+        one launch per direction for all of it (hip.losses.combine)."""
+        total, rep = hl.combine(terms, gain)
         for k, v in rep.items():
             self.report(prefix + k, v)
         return total
@@ -306,31 +260,21 @@ class StyleGAN2Loss(Loss):
     def d_real_loss(self, *args, gain=1.0, **kwargs):
         return self._finish(self.d_real_terms(*args, **kwargs), 'Loss/D/', gain)
 
-    def accumulate_gradients(self, phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, cur_nimg):
+    def accumulate_gradients(self, phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, cur_nimg,
+                             trunks=None):
+        """trunks: this micro-batch's (G's, D's) trunk output of precompute_D_trunk, read by the main phases (Gmain: both, D's without its graph;
+        Dmain: D's, its backward included).  None: each phase evaluates the trunks it needs itself."""
         assert phase in ['Gmain', 'Greg', 'Gboth', 'Dmain', 'Dreg', 'Dboth']
-        if self.share_D_trunk != 'iteration':
-            self._trunk_cache.clear()          # nothing is carried across phases unless the iteration driver parked a trunk for this iteration
         if self.pl_weight == 0:
             phase = {'Greg': 'none', 'Gboth': 'Gmain'}.get(phase, phase)
         if self.r1_gamma == 0:
             phase = {'Dreg': 'none', 'Dboth': 'Dmain'}.get(phase, phase)
-        g_body = self.G.backbone[0].body if hasattr(self.G, 'backbone') else None
-        if phase not in ('Gmain', 'Gboth') and g_body is not None and getattr(g_body, 'injected', None):
-            g_body.injected = None     # a parked G-trunk evaluation belongs to this iteration's Gmain only
-        # A trunk evaluation parked for this call (detr_backbone.ResNet50Body.injected, keyed by the batch's address) must not outlive it: after a miss
-        # or an exception a later batch at the same address would otherwise be served stale features.  (Iteration-level sharing parks G's trunks of
-        # ALL micro-batches before Gmain: those stay until the phase after Gmain begins, see above.)
         if isinstance(background, torch.Tensor) and background.is_cuda:
             core.zero_arena_begin(background.device)      # one fill for the phase's small accumulation targets (hip.core._ZeroArena)
         try:
-            self._run_phase(phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain)
-        except BaseException:
-            self._drop_parked_trunks()
-            raise
+            self._run_phase(phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, trunks)
         finally:
             core.zero_arena_end()
-        if self.share_D_trunk != 'iteration' or phase not in ('Gmain', 'Gboth'):
-            self._drop_parked_trunks()
 
     def g_pl_loss(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=1.0):
         """Path-length regularisation (loss.py:119-142): the first `batch / pl_batch_shrink` samples, || d(bbox_fake . noise) / d z || against
@@ -370,41 +314,37 @@ class StyleGAN2Loss(Loss):
         self.last = dict(r1_penalty=r1_penalty.detach(), r1_grads=r1_grads.detach(), real_logits=real_logits.detach())
         return loss_Dr1.mean().mul(gain)
 
-    def _run_phase(self, phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain):
+    def _run_phase(self, phase, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, trunks):
         # 'Gboth' / 'Dboth' (no lazy regularisation: reg_interval None) = the main phase, then the regulariser on a forward pass of its own.
         # The reference shares Dreal's forward with R1 in 'Dboth' (loss.py:162-217): same expected gradient, independent dropout draws here.
         if phase in ('Greg', 'Gboth'):
             if phase == 'Gboth':
-                self._run_phase('Gmain', bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain)
+                self._run_phase('Gmain', bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, trunks)
             self.g_pl_loss(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=gain).backward()
         if phase in ('Dreg', 'Dboth'):
             if phase == 'Dboth':
-                self._run_phase('Dmain', bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain)
+                self._run_phase('Dmain', bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gen_z, gen_c, gain, trunks)
             self.d_r1_loss(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gain=gain).backward()
         if phase == 'Gmain':
-            self.g_main_loss(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=gain).backward()
+            self.g_main_loss(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=gain, trunks=trunks).backward()
         if phase == 'Dmain':
             if self.share_D_trunk and hasattr(self.D, 'trunk'):   # True / 'phase' / 'iteration'
-                cached = self._cached_trunk(background, detach=False, pop=True)
-                if cached is None:
-                    self._dual_trunks(background)      # the generator's (no-grad) trunk beside the phase's one D-trunk evaluation
-                if self.pair_D_passes and hasattr(self.D, 'forward_pair'):
+                # the phase's one D-trunk evaluation (with the generator's no-grad trunk grouped beside it), unless the iteration's is handed in
+                bbox_fake, trunk = self._generate_for_D(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c,
+                                                        None if trunks is None else trunks[1])
+                if self.pair_D_passes:
                     # both D passes of the phase as ONE batch of 2B layouts (Discriminator.forward_pair): half the transformer / head launches
-                    bbox_fake = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True)
-                    trunk = cached if cached is not None else self.D.trunk(background)
-                    gen_out, real_out = self.D.forward_pair(bbox_fake, bbox_real.detach(), bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, trunk_out=trunk)
-                    t_gen = self.d_gen_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gen_out=gen_out)
-                    t_real = self.d_real_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, real_out=real_out)
-                elif cached is not None:
-                    t_gen = self.d_gen_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=cached)
-                    t_real = self.d_real_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, trunk_out=cached)
+                    gen_out, real_out = self.D.forward_pair(bbox_fake, bbox_real.detach(), bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c,
+                                                            trunk_out=trunk)
                 else:
-                    trunk = self.D.trunk(background)
-                    t_gen = self.d_gen_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=trunk)
-                    t_real = self.d_real_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, trunk_out=trunk)
+                    trunk = trunk if trunk is not None else self.D.trunk(background)
+                    gen_out = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True, trunk_out=trunk)
+                    real_out = None
+                t_gen = self.d_gen_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gen_out=gen_out)
+                t_real = self.d_real_terms(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, trunk_out=trunk, real_out=real_out)
                 # one backward: the trunk sees the summed gradient of both passes; mean(gen terms) + mean(real terms) = one combine over all of them
                 self._finish(t_gen + t_real, 'Loss/D/', gain).backward()
             else:
-                self._dual_trunks(background)          # reference call pattern: the generator's trunk beside the trunk of D(fake); D(real) evaluates its own
+                # reference call pattern: D(fake) groups its trunk with the generator's (d_gen_terms); D(real) evaluates its own
                 self.d_gen_loss(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, gain=gain).backward()
                 self.d_real_loss(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c, gain=gain).backward()

@@ -318,10 +318,15 @@ class Generator(nn.Module):
         self.fc_out_cls = Linear(hidden_dim, num_bbox_labels)
         self.fc_text_len_rec = Linear(hidden_dim, max_text_length)
 
-    def forward(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False):
+    def trunk(self, background, body_out=None):
+        """ResNet trunk + position encoding of the backgrounds (reference: the first statement of G.forward, training/networks_detr.py:134-136),
+        as Discriminator.trunk.  body_out: the trunk body's output, already computed (detr_backbone.dual_trunk_forward)."""
         if isinstance(background, (list, torch.Tensor)):
             background = nested_tensor_from_tensor_list(background)
-        bg_feat, pos = self.backbone(background)
+        return self.backbone(background, body_out)
+
+    def forward(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, trunk_out=None):
+        bg_feat, pos = self.trunk(background) if trunk_out is None else trunk_out
         bg_feat, mask = bg_feat[-1].decompose()
         assert mask is not None
 
@@ -416,13 +421,13 @@ class Discriminator(nn.Module):
         self.bbox_embed_uncond = Linear(hidden_dim, 4)
         self.fc_out_cls_uncond = Linear(hidden_dim, num_bbox_labels)
 
-    def trunk(self, background):
+    def trunk(self, background, body_out=None):
         """ResNet trunk + position encoding of the backgrounds (reference: the first statement of D.forward,
         training/networks_detr.py:382-385).  Deterministic in train mode (FrozenBatchNorm, no dropout), so one
-        evaluation can serve every D pass of a phase that sees the same backgrounds (`trunk_out=`)."""
+        evaluation can serve every D pass of a phase that sees the same backgrounds (`trunk_out=`).  body_out: as Generator.trunk."""
         if isinstance(background, (list, torch.Tensor)):
             background = nested_tensor_from_tensor_list(background)
-        return self.backbone(background)
+        return self.backbone(background, body_out)
 
     def _logits(self, bbox, l, text_feat, text_len_feat, l_uncond, padding_mask, src, mask, pos):
         """The two discriminator scores of a batch of layouts: -> (x0, logit, x0_uncond, logit_uncond)."""

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from ..hip import core
+from .detr_backbone import BackwardStages, trunk_body
 from .networks_detr import split_list  # noqa: F401  (training_loop.py:32 imports it from networks_layoutganpp)
 
 
@@ -551,11 +552,6 @@ def load_resume(resume_pkl, G, D, G_ema):
             copy_params_and_buffers(data[name], module, require_all=False)
 
 
-def _trunk_body(module):
-    bb = getattr(module, 'backbone', None)
-    return bb[0].body if bb is not None and hasattr(bb[0], 'body') else None
-
-
 MIN_STAGE_MS = 1.5      # a backward stage shorter than this cannot hide the host's issue latency between two graph replays (collectives are host-issued)
 
 
@@ -577,7 +573,7 @@ def measure_backward_stages(loss, phase, dp, accumulate):
     """One eager forward + three-stage backward of `phase` with HIP events at the stage boundaries -> [ms of stage 1 (incl. the forward), 2, 3], or
     None when the phase has no stageable trunk.  No exchange is issued (timing only); gradients accumulate into the flat buffer as usual."""
     segs = phase.fm.stage_segments(3)
-    body = _trunk_body(phase.module)
+    body = trunk_body(phase.module)
     if segs is None or body is None or not hasattr(body, 'stages') or not torch.cuda.is_available():
         return None
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -593,11 +589,10 @@ def staged_backward(loss, phase, dp, run_stage1, between=None, exchange=None, st
     `loss.backward()`; `between(i)` (optional) is called after stage i's work has been queued (graph capture boundaries);
     `exchange(ranges)` replaces the RCCL launch (graph capture: the collectives stay outside the graphs); `stages`: the
     BackwardStages that already recorded this phase's trunk cuts (iteration-level D-trunk sharing evaluates D's trunk before the phases)."""
-    from .detr_backbone import BackwardStages
     if stages is not None:
         n_stages = stages.n_stages
     segs = phase.fm.stage_segments(n_stages)
-    body = _trunk_body(phase.module)
+    body = trunk_body(phase.module)
     if segs is None or body is None or not hasattr(body, 'stages'):
         run_stage1()
         return False
@@ -621,6 +616,44 @@ def staged_backward(loss, phase, dp, run_stage1, between=None, exchange=None, st
     return True
 
 
+def _shares_iteration(loss, phases):
+    return getattr(loss, 'share_D_trunk', None) == 'iteration' and any(p.name == 'Dmain' for p in phases)
+
+
+def trunk_pre_pass(loss, phases, batch, batch_gpu, overlap, n_stages):
+    """Iteration-level trunk sharing (StyleGAN2Loss(share_D_trunk='iteration')): every micro-batch's trunk outputs, evaluated once before the
+    phases (precompute_D_trunk) -> (a [G's, D's] list per micro-batch for accumulate_micro_batches, the BackwardStages that recorded D's trunk
+    cuts or None); (None, None) without that sharing."""
+    if not _shares_iteration(loss, phases):
+        return None, None
+    b = batch['bbox_real'].shape[0]
+    d_stages = None
+    # the trunk is cut into backward stages only if the Dmain phase will run them (a recorded cut that is never run() would leave D's
+    # trunk without gradient while its flat segment is still reduced and applied)
+    d_phase = next(p for p in phases if p.name == 'Dmain')
+    if overlap and b <= batch_gpu and d_phase.fm.stage_segments() is not None and hasattr(trunk_body(d_phase.module), 'stages'):
+        d_stages = BackwardStages(n_stages)
+    pre = [loss.precompute_D_trunk(batch['background'][s:s + batch_gpu], stages=d_stages) for s in range(0, b, batch_gpu)]
+    return [None if t is None else list(t) for t in pre], d_stages
+
+
+def accumulate_micro_batches(loss, phase, batch, batch_gpu, gen_z, gen_c, gain, cur_nimg, pre=None):
+    """The phase's forward + backward over the micro-batches of `batch` (training_loop.py:289-292).  pre: trunk_pre_pass's trunk outputs.  The
+    driver lets go of G's once Gmain has read it and of both once Dmain has (their last readers), so that their memory returns to the (graph)
+    pool there; a micro-batch with nothing left evaluates its trunks in the phase."""
+    for i, s in enumerate(range(0, batch['bbox_real'].shape[0], batch_gpu)):
+        sl = slice(s, s + batch_gpu)
+        trunks = None if pre is None or pre[i] is None else tuple(pre[i])
+        if trunks is not None and phase.name in ('Gmain', 'Gboth'):
+            pre[i][0] = None
+        if trunks is not None and phase.name == 'Dmain':
+            pre[i] = None
+        loss.accumulate_gradients(phase=phase.name, bbox_real=batch['bbox_real'][sl], bbox_class=batch['bbox_class'][sl],
+                                  bbox_text=batch['bbox_text'][sl], bbox_patch=batch['bbox_patch'][sl],
+                                  padding_mask=batch['padding_mask'][sl], background=batch['background'][sl],
+                                  real_c=batch['real_c'][sl], gen_z=gen_z[sl], gen_c=gen_c[sl], gain=gain, cur_nimg=cur_nimg, trunks=trunks)
+
+
 def training_iteration(loss, phases, dp, batch, batch_gpu, gen_z_per_phase, ema=None, batch_size=None, ema_kimg=None, cur_nimg=0, overlap=None,
                        gen_c_per_phase=None, ema_rampup=0.05, batch_idx=0):
     """One iteration = all phases (Gmain, Dmain and -- every `phase.interval`-th iteration, counted by `batch_idx` -- the regulariser phases
@@ -632,19 +665,9 @@ def training_iteration(loss, phases, dp, batch, batch_gpu, gen_z_per_phase, ema=
     """
     b = batch['bbox_real'].shape[0]
     core.reseed(batch['bbox_real'].device)   # fresh device-side dropout seed word for this iteration
-    iter_share = getattr(loss, 'share_D_trunk', None) == 'iteration' and any(p.name == 'Dmain' for p in phases)
     if overlap is None:     # overlap the exchange with backward whenever there is an exchange (one micro-batch: the last one is the only one)
         overlap = dp.world > 1
-    d_stages = None
-    if iter_share:
-        # the trunk is cut into backward stages only if the Dmain phase will run them (a recorded cut that is never run() would leave D's
-        # trunk without gradient while its flat segment is still reduced and applied)
-        d_phase = next(p for p in phases if p.name == 'Dmain')
-        if overlap and b <= batch_gpu and d_phase.fm.stage_segments() is not None and hasattr(_trunk_body(d_phase.module), 'stages'):
-            from .detr_backbone import BackwardStages
-            d_stages = BackwardStages(backward_stage_count(b))
-        for s in range(0, b, batch_gpu):
-            loss.precompute_D_trunk(batch['background'][s:s + batch_gpu], stages=d_stages)
+    pre, d_stages = trunk_pre_pass(loss, phases, batch, batch_gpu, overlap, backward_stage_count(b))
     lerp_done = False
     due = [batch_idx % getattr(p, 'interval', 1) == 0 for p in phases]
     # the fused G_ema lerp rides on the LAST optimiser step that moves G in this iteration (a Greg phase moves it again after Gmain)
@@ -659,14 +682,9 @@ def training_iteration(loss, phases, dp, batch, batch_gpu, gen_z_per_phase, ema=
         gen_c = batch['gen_c'] if gen_c_per_phase is None else gen_c_per_phase[pi]
 
         def accumulate(phase=phase, gen_z=gen_z, gen_c=gen_c):
-            for s in range(0, b, batch_gpu):
-                sl = slice(s, s + batch_gpu)
-                loss.accumulate_gradients(phase=phase.name, bbox_real=batch['bbox_real'][sl], bbox_class=batch['bbox_class'][sl],
-                                          bbox_text=batch['bbox_text'][sl], bbox_patch=batch['bbox_patch'][sl],
-                                          padding_mask=batch['padding_mask'][sl], background=batch['background'][sl],
-                                          real_c=batch['real_c'][sl], gen_z=gen_z[sl], gen_c=gen_c[sl], gain=getattr(phase, 'interval', 1), cur_nimg=cur_nimg)
+            accumulate_micro_batches(loss, phase, batch, batch_gpu, gen_z, gen_c, getattr(phase, 'interval', 1), cur_nimg, pre)
         staged = overlap and b <= batch_gpu and not regulariser      # a regulariser phase is exchanged in one piece after its backward
-        exchanged = staged_backward(loss, phase, dp, accumulate, stages=(d_stages if (iter_share and phase.name == 'Dmain') else None),
+        exchanged = staged_backward(loss, phase, dp, accumulate, stages=(d_stages if phase.name == 'Dmain' else None),
                                     n_stages=backward_stage_count(b)) if staged else (accumulate() or False)
         phase.module.requires_grad_(False)
         fe = ema.fused(phase, batch_size, ema_kimg, cur_nimg, ema_rampup) if (ema is not None and not regulariser and last_of_fm[id(phase.fm)] == pi) else None
@@ -702,7 +720,7 @@ class GraphedIteration(object):
         dev = batch['bbox_real'].device
         b = batch['bbox_real'].shape[0]
         self.pre_graph = None
-        iter_share = getattr(loss, 'share_D_trunk', None) == 'iteration' and any(p.name == 'Dmain' for p in phases)
+        iter_share = _shares_iteration(loss, phases)
         if overlap is None:
             overlap = dp.world > 1
         pool = torch.cuda.graph_pool_handle() if (iter_share or overlap) else None
@@ -715,9 +733,7 @@ class GraphedIteration(object):
             def once(ph=ph):
                 core.reseed(dev)
                 gen_z = torch.randn(b, batch['bbox_class'].shape[1], z_dim, device=dev)
-                loss.accumulate_gradients(phase=ph.name, bbox_real=batch['bbox_real'], bbox_class=batch['bbox_class'], bbox_text=batch['bbox_text'],
-                                          bbox_patch=batch['bbox_patch'], padding_mask=batch['padding_mask'], background=batch['background'],
-                                          real_c=batch['real_c'], gen_z=gen_z, gen_c=batch['gen_c'], gain=1, cur_nimg=0)
+                accumulate_micro_batches(loss, ph, batch, batch_gpu, gen_z, batch['gen_c'], 1, 0)
             cur = torch.cuda.current_stream()
             st = self.capture_stream if self.capture_stream is not None else cur
             st.wait_stream(cur)
@@ -728,18 +744,13 @@ class GraphedIteration(object):
             self.stage_ms = dp.agree_min(self.stage_ms)      # one decision for all ranks (every rank takes this branch: same phases, same batch)
             ph.module.requires_grad_(False)
             self.n_stages = backward_stage_count(b, self.stage_ms)
-        d_stages = None
+        pre = d_stages = None
         if iter_share:
-            # D's trunk forward gets its own graph, replayed before the phases; its activations stay alive in the shared pool until
-            # the Dmain graph (captured below, replayed after it) runs the trunk's backward
-            d_phase = next(p for p in phases if p.name == 'Dmain')
-            if overlap and b <= batch_gpu and d_phase.fm.stage_segments() is not None and hasattr(_trunk_body(d_phase.module), 'stages'):
-                from .detr_backbone import BackwardStages
-                d_stages = BackwardStages(self.n_stages)
+            # the trunks' forward gets its own graph, replayed before the phases; its activations stay alive in the shared pool until
+            # the Gmain / Dmain graphs (captured below, replayed after it) run the trunks' backward
             self.pre_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.pre_graph, pool=pool, stream=self.capture_stream):
-                for s in range(0, b, batch_gpu):
-                    loss.precompute_D_trunk(batch['background'][s:s + batch_gpu], stages=d_stages)
+                pre, d_stages = trunk_pre_pass(loss, phases, batch, batch_gpu, overlap, self.n_stages)
         for phase in phases:
             for m in (loss.G, loss.D):
                 if not getattr(m, 'static_shapes', False):
@@ -763,12 +774,7 @@ class GraphedIteration(object):
                 core.reseed(dev)
                 phase.fm.gflat.zero_()
                 gen_z = torch.randn(b, batch['bbox_class'].shape[1], z_dim, device=dev)
-                for s in range(0, b, batch_gpu):
-                    sl = slice(s, s + batch_gpu)
-                    loss.accumulate_gradients(phase=phase.name, bbox_real=batch['bbox_real'][sl], bbox_class=batch['bbox_class'][sl],
-                                              bbox_text=batch['bbox_text'][sl], bbox_patch=batch['bbox_patch'][sl],
-                                              padding_mask=batch['padding_mask'][sl], background=batch['background'][sl],
-                                              real_c=batch['real_c'][sl], gen_z=gen_z[sl], gen_c=batch['gen_c'][sl], gain=1, cur_nimg=0)
+                accumulate_micro_batches(loss, phase, batch, batch_gpu, gen_z, batch['gen_c'], 1, 0, pre)
             begin()
             try:
                 if staged:
@@ -780,7 +786,7 @@ class GraphedIteration(object):
                         if i < nst:
                             begin()
                     staged_backward(loss, phase, dp, stage1, between=between, exchange=lambda ranges: None,
-                                    stages=(d_stages if (iter_share and phase.name == 'Dmain') else None), n_stages=nst)
+                                    stages=(d_stages if phase.name == 'Dmain' else None), n_stages=nst)
                 else:
                     stage1()
                     end(None)

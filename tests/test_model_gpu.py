@@ -1,7 +1,9 @@
 """GPU parity of the module-level hot path (seam 1) against (a) golden vectors captured from the reference
 and (b) the CPU oracle on seeded inputs.  Tolerance: 1e-3 relative fp32 on outputs / losses / bbox
 (north_star); most checks are far tighter and say so."""
+import gc
 import os
+import weakref
 
 import numpy as np
 import pytest
@@ -595,8 +597,21 @@ def test_iteration_level_D_trunk_sharing_matches_reference_call_pattern(dev):
     z = [zg.to(dev), zd.to(dev)]
     tl.training_iteration(StyleGAN2Loss(dev, G, D, share_D_trunk=False), [pG, pD], dp, batch, 2, z)
     loss_it = StyleGAN2Loss(dev, G, D, share_D_trunk='iteration')
+    # weak references to the features and masks of every pre-pass trunk output and to the tensors their views are of (the position encoding is a
+    # constant its module caches)
+    handed_out = []
+    precompute = loss_it.precompute_D_trunk
+
+    def spy_pre(*a, **k):
+        out = precompute(*a, **k)
+        for feats, _ in (t for t in out if t is not None):
+            ts = [f.tensors for f in feats] + [f.mask for f in feats]
+            handed_out.extend(weakref.ref(t) for t in ts + [t._base for t in ts if t._base is not None])
+        return out
+    loss_it.precompute_D_trunk = spy_pre
     tl.training_iteration(loss_it, [pG, pD], dp, batch, 2, z)
-    assert not loss_it._trunk_cache, 'trunk cache must be consumed by Dmain'
+    gc.collect()
+    assert handed_out and all(r() is None for r in handed_out), 'pre-pass trunk outputs must be released once Dmain has consumed them'
     for name in ('Gmain', 'Dmain'):
         a, b = grads[name]
         e = ((a - b).norm() / a.norm()).item()
