@@ -29,6 +29,8 @@
  *   ldetr_resample_coeffs, ldetr_resize_normalize_u8
  *                                 PIL resize + normalise of the page background: training/dataset_layoutganpp.py:330-338
  *   ldetr_lsap_f64                scipy.optimize.linear_sum_assignment as used at metrics/metric_layoutnet.py:111,125,240
+ *   ldetr_layoutnet_features_f32  LayoutNet.extract_features, the feature network of the layout FID: training/networks_layoutnet.py:48-66
+ *   ldetr_feature_stats_f64       FeatureStats.append with capture_mean_cov: metrics/metric_utils_layout.py:97-112
  *   ldetr_box_giou_pairwise_f32   box_cxcywh_to_xyxy + box_iou + generalized_box_iou: detr_util/box_ops.py:19-71
  *   ldetr_bmm_strided_f32         torch.bmm inside nn.MultiheadAttention when the regulariser phases differentiate it twice:
  *                                 training/loss.py:119-142 (path length), 207-215 (R1); hip/composite.py
@@ -439,6 +441,24 @@ int ldetr_layout_losses_bwd_f32(const float* grads, const float* grad_losses, in
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;
  * row_ind / col_ind: [batch][n] int32 outputs with scipy's ordering (row_ind sorted ascending). n <= 64. */
 int ldetr_lsap_f64(const double* cost, int batch, int n, int maximize, int* row_ind, int* col_ind, void* stream);
+
+/* LayoutNet.extract_features (training/networks_layoutnet.py:48-66) in one launch: bbox [B][N][4] fp32 (xywh), label [B][N] int64,
+ * padding_mask [B][N] (non-zero = padded) -> out [B][256] fp32, row 0 (the class token) of the four-layer post-norm encoder (d_model 256,
+ * 4 heads, feed-forward width 128, dropout off).  N + 1 <= 16.  label_map (HOST memory, map_len <= 16 entries, may be NULL with map_len 0):
+ * a label l < map_len is replaced by label_map[l] before the embedding lookup (the net effect of label_idx_replace / label_idx_replace_2,
+ * :50-61); the caller's labels are not modified.  Map entries are checked here, before the launch; the labels themselves live on the device:
+ * a valid element whose (mapped) label is outside [0, num_label) turns that sample's 256 features into NaN, nothing is read out of bounds.
+ * weights: one packed fp32 buffer of weights_len = 256 num_label + 1453312 floats in this order (row-major, nn.Module layouts):
+ *   emb_label.weight, fc_bbox.weight, fc_bbox.bias, enc_fc_in.weight, enc_fc_in.bias, enc_transformer.token, then per layer 0..3:
+ *   self_attn.in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, norm1.weight, norm1.bias, linear1.weight, linear1.bias,
+ *   linear2.weight, linear2.bias, norm2.weight, norm2.bias. */
+int ldetr_layoutnet_features_f32(const float* bbox, const int64_t* label, const uint8_t* padding_mask, const int* label_map, int map_len,
+                                 const float* weights, int64_t weights_len, int num_label, int B, int N, float* out, void* stream);
+
+/* FeatureStats.append with capture_mean_cov (metrics/metric_utils_layout.py:97-112) on resident accumulators: x [n][F] fp32;
+ * raw_mean [F] += sum_i x_i and raw_cov [F][F] += sum_i x_i x_i^T, every product and sum in float64.  F a multiple of 16, 16 <= F <= 256.
+ * One wave owns each 16 x 16 tile of raw_cov: no atomics, the same calls give the same bits. */
+int ldetr_feature_stats_f64(const float* x, int64_t n, int F, double* raw_mean, double* raw_cov, void* stream);
 
 /* Pairwise box IoU / union / generalised IoU of detr_util/box_ops.py (box_iou :35-48, generalized_box_iou :51-71; with cxcywh != 0
  * the boxes go through box_cxcywh_to_xyxy :19-23 first), batched: boxes1 [B][N][4], boxes2 [B][M][4] fp32 (16-byte aligned rows)

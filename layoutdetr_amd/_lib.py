@@ -123,6 +123,8 @@ SIGNATURES = {
     'ldetr_adam_ema_step_f32': [_P, _P, _P, _P, _L, _L, _F, _F, _F, _F, _I, _F, _F, _F, _F, _P, _F, _P],
     'ldetr_ema_lerp_f32': [_P, _P, _L, _F, _P],
     'ldetr_lsap_f64': [_P, _I, _I, _I, _P, _P, _P],
+    'ldetr_layoutnet_features_f32': [_P, _P, _P, POINTER(c_int), _I, _P, _L, _I, _I, _I, _P, _P],
+    'ldetr_feature_stats_f64': [_P, _L, _I, _P, _P, _P],
     'ldetr_box_giou_pairwise_f32': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, c_double, _P],
     'ldetr_bmm_strided_f32': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     'ldetr_softmax_xent_fwd_f32': [_P, _L, _P, _P, _P, _P, _L, _I, _L, _F, _P],

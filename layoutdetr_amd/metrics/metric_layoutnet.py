@@ -5,6 +5,20 @@ These are tiny [B, 9, 9] tensor programs (device-side glue around the hot kernel
 import torch
 
 
+class LayoutFID(object):
+    """The feature detector of the layout FID (reference :26-35): LayoutNet with 13 labels for the dataset names the reference lists, else 5,
+    its weights from a reference `layoutnet_<dataset>.pth.tar` (strict: anything else is refused), in eval mode on `device`."""
+
+    def __init__(self, pth, device):
+        from ..training.networks_layoutnet import LayoutNet
+        num_label = 13 if any(n in pth for n in ('rico', 'enrico', 'clay', 'ads_banner_collection', 'AMT_uploaded_ads_banners', 'cgl_dataset')) else 5
+        self.model = LayoutNet(num_label).to(device)
+        state_dict = torch.load(pth, map_location=device)
+        self.model.load_state_dict(state_dict, strict=True)
+        self.model.requires_grad_(False)
+        self.model.eval()
+
+
 def convert_xywh_to_ltrb(bbox):
     xc, yc, w, h = bbox
     return [xc - w / 2, yc - h / 2, xc + w / 2, yc + h / 2]

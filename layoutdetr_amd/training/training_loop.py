@@ -852,6 +852,21 @@ class InfiniteSampler(torch.utils.data.Sampler):
             idx += 1
 
 
+def assemble_batch(samples, real_c, G, background_size, device):
+    """One collated DataLoader batch -> the keyword tensors G / D / the loss take, on `device` (reference training_loop.py:246-264): device collate,
+    strings -> tokens ONCE (the reference re-tokenises inside each forward), the 0-stride patch placeholder, the page background resized and
+    normalised on the GPU.  Shared by the training loop and the metric passes (metrics/metric_utils_layout.py)."""
+    from .dataset_layoutganpp import batch_backgrounds_to_device, patch_placeholder_to_device
+    texts = list(map(list, zip(*samples['texts']))) if isinstance(samples.get('texts'), (list, tuple)) else samples['texts']   # :246
+    if isinstance(texts, list) and hasattr(G, 'tokenizer'):
+        from .networks_detr import _coerce_text
+        texts = _coerce_text(G, texts, device)
+    return dict(bbox_real=samples['bboxes'].to(device).float(), bbox_class=samples['labels'].to(device).long(), bbox_text=texts,
+                bbox_patch=patch_placeholder_to_device(samples['patches'], device), padding_mask=~samples['mask'].to(device).bool(),
+                background=batch_backgrounds_to_device(samples['background'], background_size, device),
+                real_c=real_c.to(device))
+
+
 def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={}, data_loader_kwargs={}, G_kwargs={}, D_kwargs={},
                   G_opt_kwargs={}, D_opt_kwargs={}, augment_kwargs=None, loss_kwargs={}, metrics=[], random_seed=0, num_gpus=1, rank=0,
                   batch_size=4, batch_gpu=4, ema_kimg=10, ema_rampup=0.05, G_reg_interval=None, D_reg_interval=16, augment_p=0,
@@ -864,8 +879,13 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     Also as the reference: the UP-DETR checkpoint into G / D / G_ema when `pretrained/up-detr-pre-training-60ep-imagenet.pth` exists
     (:137-139), `resume_pkl` (:140-146), one flat broadcast per module (:176-179), per-phase latents AND conditioning labels (:257-263),
     `ema_rampup` (:321-323), per-tick statistics summed over ranks in float64 + `stats.jsonl` (:428-447), network snapshots with the
-    cross-rank consistency check (:395-412).  NOT done here (a note is printed): augment pipe, ADA, image snapshots, metric evaluation,
-    tensorboard — SURVEY §8 marks them outside the hot path.  Returns dict(stats of the last tick, G, D, G_ema, snapshot_pkl)."""
+    cross-rank consistency check (:395-412), and after every snapshot the layout metrics named in `metrics` on G_ema (:413-426; metrics/metric_main.py:
+    layout FID, overlap / alignment / layout-wise IoU / DocSim, `_train` on the training set, `_val` on the validation set).  Their results go to
+    `metric-<name>.jsonl`, into the next `stats.jsonl` line as `Metrics/<key>` and into the returned dict; an evaluation (calc_metric) leaves G_ema and the torch /
+    numpy generator states as it found them, so training does not depend on whether metrics ran.  A metric this package does not register (the
+    image metrics: `train.py`'s default `fid50k_full`) is skipped with one printed note.  NOT done here (a note is printed): augment pipe, ADA,
+    image snapshots, tensorboard — SURVEY §8 marks them outside the hot path.
+    Returns dict(stats of the last tick, G, D, G_ema, snapshot_pkl, metrics)."""
     import json
     import os
     import time
@@ -915,7 +935,7 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     dp = DataParallelStep(world_size=num_gpus)
     ema = EmaTracker(phases[0], G_ema)
     if rank == 0:
-        print('Not run on this path: augment pipe, ADA, image snapshots, metrics (outside the hot path)')
+        print('Not run on this path: augment pipe, ADA, image snapshots (outside the hot path)')
         print(f'Training for {total_kimg} kimg...')
     cur_nimg, cur_tick, tick_start_nimg, tick_start = resume_kimg * 1000, 0, resume_kimg * 1000, time.time()
     batch_idx = 0
@@ -925,18 +945,15 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     stats_jsonl = open(os.path.join(run_dir, 'stats.jsonl'), 'wt') if (rank == 0 and run_dir and os.path.isdir(run_dir)) else None     # :200-202
     snapshot_pkl = None
     labelled = training_set.label_dim > 0 and hasattr(training_set, 'get_label')
+    from ..metrics import metric_main
+    run_metrics = [m for m in metrics if metric_main.is_valid_metric(m)]
+    if rank == 0 and len(run_metrics) != len(metrics):
+        print('Metrics not evaluated on this path (not registered in layoutdetr_amd.metrics.metric_main): ' + ', '.join(m for m in metrics if m not in run_metrics))
+    metric_results, pending_metrics = {}, {}
     while True:
         samples, real_c = next(it)
-        texts = list(map(list, zip(*samples['texts']))) if isinstance(samples.get('texts'), (list, tuple)) else samples['texts']   # :246
         b = samples['bboxes'].shape[0]
-        if isinstance(texts, list):     # strings -> tokens ONCE per iteration (the reference re-tokenises inside each of the 5 G/D forwards)
-            from .networks_detr import _coerce_text
-            texts = _coerce_text(G, texts, device)
-        from .dataset_layoutganpp import batch_backgrounds_to_device, patch_placeholder_to_device
-        batch = dict(bbox_real=samples['bboxes'].to(device).float(), bbox_class=samples['labels'].to(device).long(), bbox_text=texts,
-                     bbox_patch=patch_placeholder_to_device(samples['patches'], device), padding_mask=~samples['mask'].to(device).bool(),
-                     background=batch_backgrounds_to_device(samples['background'], training_set.background_size_for_training, device),
-                     real_c=real_c.to(device))
+        batch = assemble_batch(samples, real_c, G, training_set.background_size_for_training, device)
         # :257-263: one set of latents AND one set of conditioning labels (labels of random dataset items) PER PHASE
         gen_z = [torch.randn(b, batch['bbox_class'].shape[1], G.z_dim, device=device) for _ in phases]
         if labelled:
@@ -960,14 +977,27 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
             print(f'tick {cur_tick:<5d} kimg {cur_nimg / 1e3:<8.1f} sec/kimg {(now - tick_start) / max(cur_nimg - tick_start_nimg, 1) * 1e3:<7.2f} ' +
                   ' '.join(f'{k.split("/")[-1]} {v:.3f}' for k, v in sorted(last.items()) if k.startswith('Loss/scores')))
             if stats_jsonl is not None:
-                stats_jsonl.write(json.dumps(dict(tick_stats, timestamp=time.time(), **{'Progress/kimg': dict(num=1, mean=cur_nimg / 1e3, std=0.0)})) + '\n')
+                stats_jsonl.write(json.dumps(dict(tick_stats, timestamp=time.time(), **{'Progress/kimg': dict(num=1, mean=cur_nimg / 1e3, std=0.0)},
+                                                  **{f'Metrics/{k}': dict(num=1, mean=v, std=0.0) for k, v in pending_metrics.items()})) + '\n')
                 stats_jsonl.flush()
+        pending_metrics = {}
         if abort_fn is not None and abort_fn():
             done = True
         # :395-412: network snapshot (every `network_snapshot_ticks` ticks and at the end), consistency-checked across ranks
         if network_snapshot_ticks is not None and (done or cur_tick % network_snapshot_ticks == 0) and run_dir and os.path.isdir(run_dir):
             snapshot_pkl = os.path.join(run_dir, f'network-snapshot-{cur_nimg // 1000:06d}.pkl')
             save_snapshot(snapshot_pkl, G, D, G_ema, training_set_kwargs, num_gpus=num_gpus, rank=rank)
+            # :413-426: evaluate the metrics on the snapshot's G_ema
+            if run_metrics:
+                if rank == 0:
+                    print('Evaluating metrics...')
+                for metric in run_metrics:
+                    result = metric_main.calc_metric(metric=metric, run_dir=run_dir, G=G_ema, dataset_kwargs=validation_set_kwargs if '_val' in metric else training_set_kwargs,
+                                                     num_gpus=num_gpus, rank=rank, device=device)
+                    if rank == 0:
+                        metric_main.report_metric(result, run_dir=run_dir, snapshot_pkl=snapshot_pkl)
+                    pending_metrics.update(result.results)
+                metric_results.update(pending_metrics)
         cur_tick += 1
         tick_start_nimg, tick_start = cur_nimg, time.time()
         if progress_fn is not None:
@@ -975,7 +1005,11 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
         if done:
             break
     if stats_jsonl is not None:
+        if pending_metrics:      # the metrics of the final snapshot: there is no next tick to carry them
+            stats_jsonl.write(json.dumps(dict({f'Metrics/{k}': dict(num=1, mean=v, std=0.0) for k, v in pending_metrics.items()}, timestamp=time.time(),
+                                              **{'Progress/kimg': dict(num=1, mean=cur_nimg / 1e3, std=0.0)})) + '\n')
         stats_jsonl.close()
+    last.update({f'Metrics/{k}': v for k, v in metric_results.items()})
     last['cur_nimg'] = cur_nimg
     last['total_sec'] = time.time() - start_time
-    return dict(stats=last, G=G, D=D, G_ema=G_ema, snapshot_pkl=snapshot_pkl, stats_detail=tick_stats)
+    return dict(stats=last, G=G, D=D, G_ema=G_ema, snapshot_pkl=snapshot_pkl, stats_detail=tick_stats, metrics=metric_results)
