@@ -26,6 +26,8 @@
  *   ldetr_demod_*_f32             demodulation coefficients of modulated_conv2d: training/networks_stylegan2.py:57-61
  *   ldetr_layout_losses_*_f32     compute_overlap / compute_alignment / generalized_iou_loss / mse on the generated boxes:
  *                                 metrics/metric_layoutnet.py:153-201,245-275, training/loss.py:94-97
+ *   ldetr_layout_finish_f32       jitter, horizontal alignment, de_overlap, overlap / alignment scores and the argsort of generated
+ *                                 layouts: generate.py:88-136,309-329, generate_util.py:100-148,424-450
  *   ldetr_resample_coeffs, ldetr_resize_normalize_u8
  *                                 PIL resize + normalise of the page background: training/dataset_layoutganpp.py:330-338
  *   ldetr_lsap_f64                scipy.optimize.linear_sum_assignment as used at metrics/metric_layoutnet.py:111,125,240
@@ -436,6 +438,17 @@ int ldetr_demod_bwd_f32(const float* weight, int64_t so, int64_t si, int64_t sh,
 int ldetr_layout_losses_f32(const float* bbox, const float* bbox_ref, const uint8_t* valid, int B, int N, float* losses,
                             float* grads, void* stream);
 int ldetr_layout_losses_bwd_f32(const float* grads, const float* grad_losses, int B, int N, float* dbbox, void* stream);
+
+/* Finishing, scoring and ranking of C x K generated layouts in one launch (generate_util.py:424-450: jitter, horizontal_center_aligned /
+ * horizontal_left_aligned, de_overlap, compute_overlap, compute_alignment, np.argsort(overlap)).  bbox_in / bbox_out [C][K][N][4]
+ * (xc, yc, w, h; may alias), N <= 16, 1 <= K <= 1024; num [C][K]: length of the valid prefix of each layout; factors [C][K][N][4] or NULL
+ * (NULL: nothing is jittered) with jitter [C][K] or NULL (non-zero: bbox *= factors on all N slots); mode [C][K]: 0 none (no alignment,
+ * no de_overlap), 1 centre, 2 left.  de_overlap has the reference's sequential semantics: two passes over the ordered pairs (i, j != i) of
+ * the valid prefix, every read sees the updates made earlier in the pass; fp32 in the reference's operation order, no fma contraction.
+ * overlap, alignment [C][K]: the per-sample values of metrics/metric_layoutnet.py:153-201 on the finished boxes; order [C][K]: candidate
+ * indices in stable ascending order of overlap[c], NaN last.  C * K == 0 returns 0 without touching a pointer. */
+int ldetr_layout_finish_f32(const float* bbox_in, const int* num, const float* factors, const unsigned char* jitter, const unsigned char* mode,
+                            float* bbox_out, float* overlap, float* alignment, int* order, int C, int K, int N, void* stream);
 
 /* Batched linear-sum-assignment (Hungarian / shortest augmenting path) on device.
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;

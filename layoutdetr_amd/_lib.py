@@ -154,6 +154,7 @@ SIGNATURES = {
     'ldetr_demod_bwd_f32': [_P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'ldetr_layout_losses_f32': [_P, _P, _P, _I, _I, _P, _P, _P],
     'ldetr_layout_losses_bwd_f32': [_P, _P, _I, _I, _P, _P],
+    'ldetr_layout_finish_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     'ldetr_resample_coeffs': [_I, _I, _P, _P, _L, _P],
     'ldetr_p3_split_f32': [_P, _L, _P, _L, _I, _P],
     'ldetr_p3_merge_f32': [_P, _P, _L, _L, _I, _P],

@@ -325,6 +325,18 @@ class Generator(nn.Module):
             background = nested_tensor_from_tensor_list(background)
         return self.backbone(background, body_out)
 
+    def encode_condition(self, background, bbox_class, bbox_text, padding_mask):
+        """Inference: everything of forward() that does not depend on z, once per condition (trunk, input_proj, encoder, the decoder layers'
+        memory K / V projections, label / text / text-length features) -> shared_decode.Condition for decode_candidates.  No gradients."""
+        from . import shared_decode
+        return shared_decode.encode_condition(self, background, bbox_class, bbox_text, padding_mask)
+
+    def decode_candidates(self, cond, z):
+        """Inference: z [K, N, z_dim] or [C, K, N, z_dim] against a Condition -> bbox [C, K, N, 4], equal to K forward() calls per condition
+        (training/shared_decode.py).  K * N <= 16384."""
+        from . import shared_decode
+        return shared_decode.decode_candidates(self, cond, z)
+
     def forward(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, trunk_out=None):
         bg_feat, pos = self.trunk(background) if trunk_out is None else trunk_out
         bg_feat, mask = bg_feat[-1].decompose()

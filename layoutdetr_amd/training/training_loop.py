@@ -534,19 +534,24 @@ def _plain_copy(module):
     return m.eval().requires_grad_(False)
 
 
-def load_resume(resume_pkl, G, D, G_ema):
-    """training_loop.py:141-146: G / D / G_ema from a snapshot written by save_snapshot() (a pickle of dict(G=, D=, G_ema=) modules) or a
-    torch file holding state dicts under the same keys; parameters and buffers are copied by name (require_all=False)."""
+def read_snapshot(resume_pkl):
+    """The dict(G=, D=, G_ema=, ...) inside a snapshot written by save_snapshot() (modules) or a torch file of state dicts under the same keys."""
     import pickle
     try:
         with open(resume_pkl, 'rb') as f:
-            data = pickle.load(f)
+            return pickle.load(f)
     except (pickle.UnpicklingError, ModuleNotFoundError, AttributeError) as e:
         try:
-            data = torch.load(resume_pkl, map_location='cpu')
+            return torch.load(resume_pkl, map_location='cpu')
         except Exception:
             raise RuntimeError(f'resume_pkl={resume_pkl!r}: neither a snapshot of this package (save_snapshot) nor a torch file of state dicts; '
                                f'pickles of the reference\'s own classes need the reference tree + its legacy loader ({e})')
+
+
+def load_resume(resume_pkl, G, D, G_ema):
+    """training_loop.py:141-146: G / D / G_ema from a snapshot written by save_snapshot() (a pickle of dict(G=, D=, G_ema=) modules) or a
+    torch file holding state dicts under the same keys; parameters and buffers are copied by name (require_all=False)."""
+    data = read_snapshot(resume_pkl)
     for name, module in (('G', G), ('D', D), ('G_ema', G_ema)):
         if name in data and data[name] is not None:
             copy_params_and_buffers(data[name], module, require_all=False)
