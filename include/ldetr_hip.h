@@ -48,7 +48,7 @@ extern "C" {
 
 /* Human-readable message of the last failing call on this thread. */
 const char* ldetr_last_error(void);
-/* ABI version; bumped whenever a signature changes. */
+/* ABI version (25); bumped whenever a signature changes. */
 int ldetr_abi_version(void);
 
 /* Development aid (tools/trace_tiles.py): while `buffer` (device memory, 5 int64 per block of the traced launch) is non-NULL,
@@ -188,74 +188,6 @@ int ldetr_attention_bwd_f32(const float* q, int64_t ldq, const float* k, int64_t
                             float* dv, int64_t lddv, int B, int H, int Lq, int Lk, int head_dim, float scale,
                             float p_drop, uint64_t seed, const uint64_t* seed_ptr, int causal, void* stream);
 
-/* ypos (optional, with pos [pos_rows, D]): second output ypos[row] = y[row] + pos[row % pos_rows] — the position-embedded copy the
- * next attention block projects q and k from (training/detr_transformer.py:207,277 form it with one extra kernel per layer);
- * dy2 (optional): gradient that arrived through ypos, summed into dy as it is loaded. */
-int ldetr_layernorm_fwd_pos_f32(const float* x, const float* residual, const float* gamma, const float* beta, float* y,
-                                float* z, float* mean, float* rstd, int64_t rows, int D, float eps, float p_drop,
-                                uint64_t seed, const uint64_t* seed_ptr, const float* pos, int64_t pos_rows, float* ypos,
-                                void* stream);
-
-/* The same with the residual branch given as `n_parts` partial sums parts[s][rows][D] (pitch part_stride floats between slices) plus a
- * column bias: r = part_bias + sum_s parts[s], added in slice order (deterministic).  This is where the hidden-slice contributions of the
- * fused feed-forward block (ldetr_ffn_fwd_f32) are reduced.  n_parts = 0: `parts` is the plain residual (== ldetr_layernorm_fwd_pos_f32). */
-int ldetr_layernorm_fwd_parts_f32(const float* x, const float* parts, int n_parts, int64_t part_stride, const float* part_bias,
-                                  const float* gamma, const float* beta, float* y, float* z, float* mean, float* rstd,
-                                  int64_t rows, int D, float eps, float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                                  const float* pos, int64_t pos_rows, float* ypos, void* stream);
-
-/* Self-attention sub-block of the short-sequence stacks (nn.MultiheadAttention(256, 8) with q = k = v = x, L <= 16 tokens per sample:
- * training/detr_transformer.py:273-274; nn.TransformerEncoderLayer at training/util.py:21-26, networks_detr.py:243,269,275) as ONE
- * forward launch (csrc/mha_small.hip): packed projection, masked softmax attention with dropout on the probabilities, and the output
- * projection's per-head contributions.
- *   x [B*L][ldx], w_in [768][256], b_in [768], w_out [256][256], kpm [B][L] (nonzero = masked key) or NULL
- *   -> qkv [B*L][768] (projection incl. bias, q unscaled), o [B*L][256] (attention output), lse [B][8][L]: what
- *      ldetr_attention_bwd_f32 reads (same dropout element index, same seed);
- *   -> ypart [8][B*L][256]: out_proj contributions per head WITHOUT its bias (reduce with ldetr_layernorm_fwd_parts_f32). */
-int ldetr_mha_small_fwd_f32(const float* x, int64_t ldx, const float* w_in, const float* b_in, const float* w_out,
-                            const uint8_t* kpm, float* qkv, float* o, float* lse, float* ypart,
-                            int B, int L, int D, int H, float scale, float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                            void* stream);
-
-/* Cross-attention sub-block of a decoder layer (training/detr_transformer.py:277-280) with <= 16 queries per sample onto <= 64 memory
- * tokens whose K / V projections already exist (k, v: [B*Lk][ldk / ldv], head h in columns 32 h .. 32 h + 31): query projection
- * (w_q, b_q = rows 0..255 of in_proj_weight / in_proj_bias), attention, per-head output projection in one launch.
- *   -> q [B*Lq][256] (projected queries incl. bias, unscaled), o [B*Lq][256], lse [B][8][Lq]: what ldetr_attention_bwd_f32 reads;
- *   -> ypart [8][B*Lq][256] as in ldetr_mha_small_fwd_f32. */
-int ldetr_mha_cross_fwd_f32(const float* x, int64_t ldx, const float* w_q, const float* b_q,
-                            const float* k, int64_t ldk, const float* v, int64_t ldv, const float* w_out,
-                            const uint8_t* kpm, float* q, float* o, float* lse, float* ypart,
-                            int B, int Lq, int Lk, int D, int H, float scale, float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                            void* stream);
-
-/* Position-wise feed-forward block linear2(dropout(relu(linear1(x)))) of the DETR layers (training/detr_transformer.py:212-214, 283-285;
- * d_model D = 256, hidden width F a multiple of 64), one launch per direction (csrc/ffn_fused.hip).
- * fwd: x [M][ldx], w1 [F][D], b1 [F], w2 [D][F] -> h [M][F] (hidden after relu + dropout, kept for the backward) and
- *      ypart [F/64][M][D]: per-hidden-slice contributions to the output WITHOUT b2 (reduce with ldetr_layernorm_fwd_parts_f32).
- * bwd: dy [M][D] (gradient of the block output) -> dxpart [F/64][M][D]: per-hidden-slice contributions to the input gradient (reduce with
- *      ldetr_layernorm_bwd_parts_f32) and, if dh is not NULL, dh [M][F] = gradient of the hidden pre-activation (relu and dropout masks
- *      applied).  The weight gradients are plain contractions over the tokens: dW2 += dy^T h, dW1 += dh^T x, db2 / db1 = their row sums
- *      (one ldetr_gemm_pair_f32 call).  p_drop / seed as in ldetr_gemm_f32's epilogue (element index = row * F + column of h). */
-int ldetr_ffn_fwd_f32(const float* x, int64_t ldx, const float* w1, const float* b1, const float* w2, float* h, float* ypart,
-                      int64_t M, int D, int F, float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream);
-int ldetr_ffn_bwd_f32(const float* dy, const float* x, int64_t ldx, const float* h, const float* w1, const float* w2,
-                      float* dxpart, float* dh, int64_t M, int D, int F, float p_drop, void* stream);
-int ldetr_layernorm_bwd2_f32(const float* dy, const float* dy2, const float* z, const float* mean, const float* rstd,
-                             const float* gamma, float* dx, float* dresidual, float* dgamma, float* dbeta, int64_t rows,
-                             int D, float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream);
-/* ... with the incoming gradient given as dy (+ dy2) + sum_s dy_parts[s][rows][D] (pitch part_stride floats), added in slice order: where the
- * hidden-slice contributions of ldetr_ffn_bwd_f32 to the feed-forward block's input gradient are reduced. */
-int ldetr_layernorm_bwd_parts_f32(const float* dy, const float* dy2, const float* dy_parts, int n_parts, int64_t part_stride,
-                                  const float* z, const float* mean, const float* rstd, const float* gamma,
-                                  float* dx, float* dresidual, float* dgamma, float* dbeta, int64_t rows, int D,
-                                  float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream);
-int ldetr_layernorm_fwd_f32(const float* x, const float* residual, const float* gamma, const float* beta, float* y,
-                            float* z, float* mean, float* rstd, int64_t rows, int D, float eps, float p_drop,
-                            uint64_t seed, const uint64_t* seed_ptr, void* stream);
-int ldetr_layernorm_bwd_f32(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
-                            float* dx, float* dresidual, float* dgamma, float* dbeta, int64_t rows, int D,
-                            float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream);
-
 /* Second stage of ldetr_torgb_bwd_f32 (ToRGBLayer backward, training/networks_stylegan2.py:349-353): dws [B][3][C] ->
  * dw[o][c] += sum_b dws[b][o][c] s[b][c] (accumulated) and ds[b][c] = sum_o dws[b][o][c] w[o][c]. */
 int ldetr_torgb_bwd_finish_f32(const float* dws, const float* s, const float* w, int B, int C, float* dw, float* ds, void* stream);
@@ -281,21 +213,44 @@ int ldetr_masked_mse_bwd_f32(const float* a, const float* b, const uint8_t* vali
  * beside its unconditional encoder (networks_detr.py:242-243), are structurally identical, independent stacks that the reference runs one after the
  * other; every launch of such a stack is a fraction of a wave of work per CU.  The entry points below take ONE or TWO argument blocks: the second
  * problem's blocks follow the first's in the same grid (the ldetr_p3_conv2d_fwd_dual idea), so two stacks advance with one launch per sub-block.
- * The argument blocks are plain structs of device pointers and sizes; the single-problem entry points above are these with n = 1. */
+ * The argument blocks are plain structs of device pointers and sizes (zero-fill the fields of the other direction); a single problem is n = 1.
+ * These are the only entry points of the four kernel families.
+ *
+ * LayerNorm with the residual chain around it (csrc/layernorm.hip).  forward: z = x + dropout(r), y = LN(z) * gamma + beta.
+ *   r_parts > 0: the residual branch is still a sum to be formed, r = r_bias + sum_s r[s][rows][D] (pitch r_part_stride floats between slices),
+ *   added in slice order (deterministic).  This is where the per-head contributions of the attention sub-blocks (ldetr_mha_small_args.ypart,
+ *   ldetr_mha_cross_args.ypart) and the hidden-slice contributions of the fused feed-forward block (ldetr_ffn_args.ypart) are reduced, together
+ *   with the bias their producers leave out.  r_parts = 0: r is the plain residual (or NULL) and r_bias is ignored.
+ *   ypos (optional, with pos [pos_rows, D]): second output ypos[row] = y[row] + pos[row % pos_rows] -- the position-embedded copy the
+ *   next attention block projects q and k from (training/detr_transformer.py:207,277 form it with one extra kernel per layer).
+ * backward: incoming gradient = dy (+ dy2) + sum_s dy_parts[s][rows][D] (pitch dy_part_stride floats), added in slice order: where the
+ *   hidden-slice contributions of the feed-forward backward (ldetr_ffn_args.dxpart) and the per-head ones of the attention backwards
+ *   (ldetr_mha_small_args.dxpart, ldetr_mha_cross_args.dxpart) to a sub-block's input gradient are reduced.  dy2 (optional): the gradient that
+ *   arrived through ypos, or any second full tensor, summed into dy as it is loaded.  dgamma / dbeta are accumulated with atomics: the caller
+ *   zeroes them (or passes running gradients). */
 typedef struct ldetr_ln_args {
     const float* x; const float* r; const float* gamma; const float* beta;       /* forward: y = LN(x + dropout(r)); r may be NULL */
-    float* y; float* z; float* mean; float* rstd;                                 /* z = pre-norm sum (kept for the backward), row statistics */
+    float* y; float* z; float* mean; float* rstd;                                 /* z = pre-norm sum (kept for the backward; optional), row statistics */
     const float* dy; float* dx; float* dr; float* dgamma; float* dbeta;            /* backward: dx = dz, dr = dz * dropout mask (optional); dgamma / dbeta += (atomics) */
     int64_t rows; int D; float eps, p_drop; uint64_t seed; const uint64_t* seed_ptr;
     const float* pos; int64_t pos_rows; float* ypos; const float* dy2;             /* second output y + pos[row % pos_rows] and its gradient */
     int r_parts; int64_t r_part_stride; const float* r_bias;                      /* forward: r = r_bias + sum of r_parts slices r[s][rows][D] */
     const float* dy_parts; int dy_nparts; int64_t dy_part_stride;                 /* backward: incoming gradient = dy (+ dy2) + sum of dy_nparts slices */
 } ldetr_ln_args;
+/* n = 1 or 2 problems of the same D (a multiple of 4 in [4, 1024]) as one launch. */
 int ldetr_layernorm_fwd_group_f32(const ldetr_ln_args* a, int n, void* stream);
 int ldetr_layernorm_bwd_group_f32(const ldetr_ln_args* a, int n, void* stream);
 /* out = base (or 0 when NULL) + sum_s parts[s], in slice order; n elements (multiple of 4), 16-byte aligned buffers. */
 int ldetr_sum_parts_f32(const float* base, const float* parts, int n_parts, int64_t part_stride, float* out, int64_t n, void* stream);
 
+/* Position-wise feed-forward block linear2(dropout(relu(linear1(x)))) of the DETR layers (training/detr_transformer.py:212-214, 283-285;
+ * d_model 256, hidden width F a multiple of 64), one launch per direction (csrc/ffn_fused.hip).
+ * fwd: x [M][ldx], w1 [F][256], b1 [F], w2 [256][F] -> h [M][F] (hidden after relu + dropout, kept for the backward) and
+ *      ypart [F/64][M][256]: per-hidden-slice contributions to the output WITHOUT b2 (reduce with ldetr_ln_args.r_parts / r_bias).
+ * bwd: dy [M][256] (gradient of the block output) -> dxpart [F/64][M][256]: per-hidden-slice contributions to the input gradient (reduce with
+ *      ldetr_ln_args.dy_parts) and, if dh is not NULL, dh [M][F] = gradient of the hidden pre-activation (relu and dropout masks
+ *      applied).  The weight gradients are plain contractions over the tokens: dW2 += dy^T h, dW1 += dh^T x, db2 / db1 = their row sums
+ *      (one ldetr_gemm_pair_f32 or ldetr_wgrad_multi_f32 call).  p_drop / seed as in ldetr_gemm_f32's epilogue (element index = row * F + column of h). */
 typedef struct ldetr_ffn_args {
     const float* x; int64_t ldx;              /* [M][ldx] block input */
     const float* w1; const float* b1;         /* [F][256], [F] */
@@ -311,10 +266,18 @@ typedef struct ldetr_ffn_args {
 int ldetr_ffn_fwd_group_f32(const ldetr_ffn_args* a, int n, void* stream);
 int ldetr_ffn_bwd_group_f32(const ldetr_ffn_args* a, int n, void* stream);
 
-/* Self-attention sub-block (ldetr_mha_small_fwd_f32's arguments) and its BACKWARD as one launch: per (sample, head) block
+/* Self-attention sub-block of the short-sequence stacks (nn.MultiheadAttention(256, 8) with q = k = v = x, L <= 16 tokens per sample:
+ * training/detr_transformer.py:273-274; nn.TransformerEncoderLayer at training/util.py:21-26, networks_detr.py:243,269,275) as ONE
+ * forward launch (csrc/mha_small.hip): packed projection, masked softmax attention with dropout on the probabilities, and the output
+ * projection's per-head contributions.
+ *   x [B*L][ldx], w_in [768][256], b_in [768], w_out [256][256], kpm [B][L] (nonzero = masked key) or NULL
+ *   -> qkv [B*L][768] (projection incl. bias, q unscaled), o [B*L][256] (attention output), lse [B][8][L]: what
+ *      ldetr_attention_bwd_f32 reads (same dropout element index, same seed);
+ *   -> ypart [8][B*L][256]: out_proj contributions per head WITHOUT its bias (reduce with ldetr_ln_args.r_parts / r_bias).
+ * Its BACKWARD as one launch: per (sample, head) block
  *   dO_h = dr_b W_out[:, 32h : 32h+32]; attention backward on the saved projection (dropout mask regenerated from the seed); the head's packed
- *   gradient dqkv [B*L][768] (operand of the weight gradient dW_in += dqkv^T x, written once); and the head's contribution to the input gradient
- *   dqkv_h W_in,h -> dxpart[h][B*L][256] (reduce with ldetr_layernorm_bwd_group_f32's dy_parts or ldetr_sum_parts_f32).
+ *   gradient dqkv [B*L][768] (operand of the weight gradient dW_in += dqkv^T x, written once; optional); and the head's contribution to the input
+ *   gradient dqkv_h W_in,h -> dxpart[h][B*L][256] (reduce with ldetr_ln_args.dy_parts or ldetr_sum_parts_f32).
  * Replaces {out_proj data gradient, ldetr_attention_bwd_f32, in_proj data gradient} = three launches of the unfused path. */
 typedef struct ldetr_mha_small_args {
     const float* x; int64_t ldx;
@@ -329,7 +292,13 @@ typedef struct ldetr_mha_small_args {
 int ldetr_mha_small_fwd_group_f32(const ldetr_mha_small_args* a, int n, void* stream);
 int ldetr_mha_small_bwd_group_f32(const ldetr_mha_small_args* a, int n, void* stream);
 
-/* Cross-attention sub-block backward (forward: ldetr_mha_cross_fwd_f32) as one launch per (sample, head): dO_h = dr_b W_out[:, head]; attention backward
+/* Cross-attention sub-block of a decoder layer (training/detr_transformer.py:277-280) with <= 16 queries per sample onto <= 64 memory
+ * tokens whose K / V projections already exist (k, v: [B*Lk][ldk / ldv], head h in columns 32 h .. 32 h + 31): query projection
+ * (w_q, b_q = rows 0..255 of in_proj_weight / in_proj_bias), attention, per-head output projection in one launch.
+ *   x [B*Lq][ldx], kpm [B][Lk] (nonzero = masked key) or NULL
+ *   -> q [B*Lq][256] (projected queries incl. bias, unscaled), o [B*Lq][256], lse [B][8][Lq]: what ldetr_attention_bwd_f32 reads;
+ *   -> ypart [8][B*Lq][256]: out_proj contributions per head WITHOUT its bias, as in ldetr_mha_small_args.
+ * Its backward as one launch per (sample, head): dO_h = dr_b W_out[:, head]; attention backward
  * on the saved q and the projected memory K / V (dK / dV written to dk / dv with pitches lddk / lddv: the grouped projection's gradient buffer);
  * dq [B*Lq][256]; dxpart[h][B*Lq][256] = dq_h W_q,h. */
 typedef struct ldetr_mha_cross_args {
@@ -344,6 +313,7 @@ typedef struct ldetr_mha_cross_args {
     const float* dr;
     float* dq; float* dk; int64_t lddk; float* dv; int64_t lddv; float* dxpart;
 } ldetr_mha_cross_args;
+int ldetr_mha_cross_fwd_f32(const ldetr_mha_cross_args* a, void* stream);
 int ldetr_mha_cross_bwd_f32(const ldetr_mha_cross_args* a, void* stream);
 
 /* Up to 8 weight gradients dW[rows][cols] += A^T B over the tokens (A [M][lda] holds the `rows` output features in columns, B [M][ldb] the `cols`

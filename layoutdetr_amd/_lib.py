@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LDETR_LIB: development aid (tools/build_variant.sh) -- an alternative build of the same library, e.g. to A/B a kernel change on one box
-ABI_VERSION = 24   # include/ldetr_hip.h; csrc/ldetr_core.cpp
+ABI_VERSION = 25   # include/ldetr_hip.h; csrc/ldetr_core.cpp
 LIB_PATH = os.environ.get('LDETR_LIB') or os.path.join(_HERE, 'lib', 'libldetr_hip.so')
 
 
@@ -101,16 +101,6 @@ SIGNATURES = {
     'ldetr_attention_fwd_f32': [_P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _I, _I, _I, _I, _I, _F, _F, c_uint64, _P, _I, _P],
     'ldetr_attention_bwd_f32': [_P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P, _L,
                                 _I, _I, _I, _I, _I, _F, _F, c_uint64, _P, _I, _P],
-    'ldetr_layernorm_fwd_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _F, c_uint64, _P, _P],
-    'ldetr_layernorm_bwd_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, c_uint64, _P, _P],
-    'ldetr_layernorm_fwd_pos_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _F, c_uint64, _P, _P, _L, _P, _P],
-    'ldetr_layernorm_fwd_parts_f32': [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _F, c_uint64, _P, _P, _L, _P, _P],
-    'ldetr_mha_small_fwd_f32': [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, c_uint64, _P, _P],
-    'ldetr_mha_cross_fwd_f32': [_P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, c_uint64, _P, _P],
-    'ldetr_ffn_fwd_f32': [_P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _F, c_uint64, _P, _P],
-    'ldetr_ffn_bwd_f32': [_P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _F, _P],
-    'ldetr_layernorm_bwd_parts_f32': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, c_uint64, _P, _P],
-    'ldetr_layernorm_bwd2_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, c_uint64, _P, _P],
     'ldetr_colsum_f32': [_P, _P, _I, _L, _I, _P],
     'ldetr_act_bwd_reduce_f32': [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _F, _F, _P],
     'ldetr_mul_reduce_f32': [_P, _P, _P, _P, _P, _I, _L, _I, _P],
@@ -141,6 +131,7 @@ SIGNATURES = {
     'ldetr_ffn_bwd_group_f32': [_P, _I, _P],
     'ldetr_mha_small_fwd_group_f32': [_P, _I, _P],
     'ldetr_mha_small_bwd_group_f32': [_P, _I, _P],
+    'ldetr_mha_cross_fwd_f32': [_P, _P],
     'ldetr_mha_cross_bwd_f32': [_P, _P],
     'ldetr_wgrad_multi_f32': [_P, _I, _P],
     'ldetr_loss_combine_fwd_f32': [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],

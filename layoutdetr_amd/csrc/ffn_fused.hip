@@ -214,17 +214,11 @@ __global__ __launch_bounds__(256) void ffn_bwd_kernel(FfnParams pa, FfnParams pb
 
 using namespace ldetr;
 
-static int ffn_check(const char* what, int64_t M, int D, int F, const void* x, int64_t ldx) {
-    LDETR_CHECK(D == FD, "%s: the fused feed-forward block is built for d_model = 256 (got %d)", what, D);
-    LDETR_CHECK(F >= FHS && F % FHS == 0, "%s: hidden width must be a multiple of 64 (got %d)", what, F);
-    LDETR_CHECK(M >= 0 && M <= (1 << 20), "%s: bad row count", what);
-    LDETR_CHECK(x && ldx >= D && ldx % 4 == 0 && (((uintptr_t)x) & 15) == 0, "%s: x must be 16-byte aligned rows with a pitch that is a multiple of 4", what);
-    LDETR_CHECK((long)M * ldx * 4 < 0x7fffffffL && (long)M * F * 4 < 0x7fffffffL && (long)(F / FHS) * M * D * 4 < 0x7fffffffL, "%s: operand above 2 GiB", what);
-    return LDETR_OK;
-}
-
 static int ffn_check_args(const char* what, const FfnParams& p, bool bwd) {
-    if (int rc = ffn_check(what, p.M, FD, p.F, p.x, p.ldx)) return rc;
+    LDETR_CHECK(p.F >= FHS && p.F % FHS == 0, "%s: hidden width must be a multiple of 64 (got %d)", what, p.F);
+    LDETR_CHECK(p.M >= 0 && p.M <= (1 << 20), "%s: bad row count", what);
+    LDETR_CHECK(p.x && p.ldx >= FD && p.ldx % 4 == 0 && (((uintptr_t)p.x) & 15) == 0, "%s: x must be 16-byte aligned rows with a pitch that is a multiple of 4", what);
+    LDETR_CHECK((long)p.M * p.ldx * 4 < 0x7fffffffL && (long)p.M * p.F * 4 < 0x7fffffffL && (long)(p.F / FHS) * p.M * FD * 4 < 0x7fffffffL, "%s: operand above 2 GiB", what);
     if (!bwd) {
         LDETR_CHECK(p.w1 && p.b1 && p.w2 && p.h && p.ypart, "%s: null pointer", what);
         LDETR_CHECK(p.p_drop >= 0.f && p.p_drop < 1.f, "%s: p_drop out of range", what);
@@ -253,21 +247,3 @@ static int ffn_launch(const ldetr_ffn_args* a, int n, bool bwd, void* stream) {
 
 extern "C" int ldetr_ffn_fwd_group_f32(const ldetr_ffn_args* a, int n, void* stream) { return ffn_launch(a, n, false, stream); }
 extern "C" int ldetr_ffn_bwd_group_f32(const ldetr_ffn_args* a, int n, void* stream) { return ffn_launch(a, n, true, stream); }
-
-extern "C" int ldetr_ffn_fwd_f32(const float* x, int64_t ldx, const float* w1, const float* b1, const float* w2, float* h, float* ypart,
-                                 int64_t M, int D, int F, float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream) {
-    if (int rc = ffn_check("ffn_fwd", M, D, F, x, ldx)) return rc;
-    FfnParams p; memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = ldx; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.h = h; p.ypart = ypart; p.M = (int)M; p.F = F;
-    p.p_drop = p_drop; p.seed = seed; p.seed_ptr = seed_ptr;
-    return ffn_launch(&p, 1, false, stream);
-}
-
-extern "C" int ldetr_ffn_bwd_f32(const float* dy, const float* x, int64_t ldx, const float* h, const float* w1, const float* w2,
-                                 float* dxpart, float* dh, int64_t M, int D, int F, float p_drop, void* stream) {
-    if (int rc = ffn_check("ffn_bwd", M, D, F, x, ldx)) return rc;
-    FfnParams p; memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = ldx; p.w1 = w1; p.w2 = w2; p.h = const_cast<float*>(h); p.M = (int)M; p.F = F; p.p_drop = p_drop;
-    p.dy = dy; p.dxpart = dxpart; p.dh = dh;
-    return ffn_launch(&p, 1, true, stream);
-}

@@ -187,19 +187,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnParams pa, LnParams pb, i
 
 using namespace ldetr;
 
-extern "C" int ldetr_layernorm_fwd_f32(const float* x, const float* residual, const float* gamma, const float* beta,
-                                       float* y, float* z, float* mean, float* rstd, int64_t rows, int D, float eps,
-                                       float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream) {
-    return ldetr_layernorm_fwd_pos_f32(x, residual, gamma, beta, y, z, mean, rstd, rows, D, eps, p_drop, seed, seed_ptr, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int ldetr_layernorm_fwd_pos_f32(const float* x, const float* residual, const float* gamma, const float* beta,
-                                           float* y, float* z, float* mean, float* rstd, int64_t rows, int D, float eps,
-                                           float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                                           const float* pos, int64_t pos_rows, float* ypos, void* stream) {
-    return ldetr_layernorm_fwd_parts_f32(x, residual, 0, 0, nullptr, gamma, beta, y, z, mean, rstd, rows, D, eps, p_drop, seed, seed_ptr, pos, pos_rows, ypos, stream);
-}
-
 static int ln_check_fwd(const LnParams& p) {
     LDETR_CHECK(p.r_parts >= 0 && (p.r_parts == 0 || (p.r && p.r_part_stride >= p.rows * p.D)), "layernorm_fwd: bad partial-sum arguments");
     LDETR_CHECK(p.x && p.gamma && p.beta && p.y, "layernorm_fwd: null pointer");
@@ -229,31 +216,6 @@ extern "C" int ldetr_layernorm_fwd_group_f32(const ldetr_ln_args* a, int n, void
     return check_launch("layernorm_fwd");
 }
 
-extern "C" int ldetr_layernorm_fwd_parts_f32(const float* x, const float* parts, int n_parts, int64_t part_stride, const float* part_bias,
-                                             const float* gamma, const float* beta, float* y, float* z, float* mean, float* rstd,
-                                             int64_t rows, int D, float eps, float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                                             const float* pos, int64_t pos_rows, float* ypos, void* stream) {
-    LnParams p; memset(&p, 0, sizeof(p));
-    p.x = x; p.r = parts; p.gamma = gamma; p.beta = beta; p.y = y; p.z = z; p.mean = mean; p.rstd = rstd;
-    p.rows = rows; p.D = D; p.eps = eps; p.p_drop = p_drop; p.seed = seed; p.seed_ptr = seed_ptr;
-    p.pos = pos; p.pos_rows = pos_rows; p.ypos = ypos;
-    p.r_parts = n_parts; p.r_part_stride = part_stride; p.r_bias = n_parts > 0 ? part_bias : nullptr;
-    return ldetr_layernorm_fwd_group_f32(&p, 1, stream);
-}
-
-// dgamma/dbeta are accumulated with atomics: the caller zeroes them (or passes running gradients).
-extern "C" int ldetr_layernorm_bwd_f32(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
-                                       float* dx, float* dresidual, float* dgamma, float* dbeta, int64_t rows, int D,
-                                       float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream) {
-    return ldetr_layernorm_bwd2_f32(dy, nullptr, z, mean, rstd, gamma, dx, dresidual, dgamma, dbeta, rows, D, p_drop, seed, seed_ptr, stream);
-}
-
-extern "C" int ldetr_layernorm_bwd2_f32(const float* dy, const float* dy2, const float* z, const float* mean, const float* rstd, const float* gamma,
-                                        float* dx, float* dresidual, float* dgamma, float* dbeta, int64_t rows, int D,
-                                        float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream) {
-    return ldetr_layernorm_bwd_parts_f32(dy, dy2, nullptr, 0, 0, z, mean, rstd, gamma, dx, dresidual, dgamma, dbeta, rows, D, p_drop, seed, seed_ptr, stream);
-}
-
 static int ln_check_bwd(const LnParams& p) {
     LDETR_CHECK(p.dy_nparts >= 0 && (p.dy_nparts == 0 || (p.dy_parts && p.dy_part_stride >= p.rows * p.D)), "layernorm_bwd: bad partial-sum arguments");
     LDETR_CHECK(p.dy && p.z && p.mean && p.rstd && p.gamma, "layernorm_bwd: null pointer");
@@ -262,6 +224,7 @@ static int ln_check_bwd(const LnParams& p) {
     return LDETR_OK;
 }
 
+// dgamma/dbeta are accumulated with atomics: the caller zeroes them (or passes running gradients).
 extern "C" int ldetr_layernorm_bwd_group_f32(const ldetr_ln_args* a, int n, void* stream) {
     LDETR_CHECK(a && (n == 1 || n == 2), "layernorm_bwd_group: 1 or 2 problems");
     LnParams p[2]; p[0] = a[0]; p[1] = n == 2 ? a[1] : a[0];
@@ -278,18 +241,6 @@ extern "C" int ldetr_layernorm_bwd_group_f32(const ldetr_ln_args* a, int n, void
     else if (nv == 3) hipLaunchKernelGGL(ln_bwd_kernel<3>, grid, 256, 0, st, p[0], p[1], nb0);
     else hipLaunchKernelGGL(ln_bwd_kernel<4>, grid, 256, 0, st, p[0], p[1], nb0);
     return check_launch("layernorm_bwd");
-}
-
-extern "C" int ldetr_layernorm_bwd_parts_f32(const float* dy, const float* dy2, const float* dy_parts, int n_parts, int64_t part_stride,
-                                             const float* z, const float* mean, const float* rstd, const float* gamma,
-                                             float* dx, float* dresidual, float* dgamma, float* dbeta, int64_t rows, int D,
-                                             float p_drop, uint64_t seed, const uint64_t* seed_ptr, void* stream) {
-    LnParams p; memset(&p, 0, sizeof(p));
-    p.dy = dy; p.z = const_cast<float*>(z); p.mean = const_cast<float*>(mean); p.rstd = const_cast<float*>(rstd);
-    p.gamma = gamma; p.dx = dx; p.dr = dresidual; p.dgamma = dgamma; p.dbeta = dbeta; p.dy2 = dy2;
-    p.dy_parts = dy_parts; p.dy_nparts = n_parts; p.dy_part_stride = part_stride;
-    p.rows = rows; p.D = D; p.p_drop = p_drop; p.seed = seed; p.seed_ptr = seed_ptr;
-    return ldetr_layernorm_bwd_group_f32(&p, 1, stream);
 }
 
 // out[rows][D] = base[rows][D] (or 0) + sum_s parts[s][rows][D], in slice order: where a gradient that travelled between sub-blocks as partial sums

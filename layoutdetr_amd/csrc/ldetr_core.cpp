@@ -64,7 +64,7 @@ extern "C" int ldetr_engine_last_launch(int32_t* info10) {
 }
 
 extern "C" const char* ldetr_last_error(void) { return ldetr::g_err; }
-extern "C" int ldetr_abi_version(void) { return 24; }
+extern "C" int ldetr_abi_version(void) { return 25; }
 // sizeof of every argument block of the group launches, in header order: the host bindings (layoutdetr_amd/_lib.py) mirror them field by field
 extern "C" int ldetr_struct_sizes(int32_t* out6) {
     if (!out6) return 1;

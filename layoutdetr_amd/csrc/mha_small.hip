@@ -858,31 +858,38 @@ static int mha_small_launch(const ldetr_mha_small_args* a, int n, bool bwd, void
 extern "C" int ldetr_mha_small_fwd_group_f32(const ldetr_mha_small_args* a, int n, void* stream) { return mha_small_launch(a, n, false, stream); }
 extern "C" int ldetr_mha_small_bwd_group_f32(const ldetr_mha_small_args* a, int n, void* stream) { return mha_small_launch(a, n, true, stream); }
 
-extern "C" int ldetr_mha_small_fwd_f32(const float* x, int64_t ldx, const float* w_in, const float* b_in, const float* w_out,
-                                       const uint8_t* kpm, float* qkv, float* o, float* lse, float* ypart,
-                                       int B, int L, int D, int H, float scale, float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                                       void* stream) {
-    LDETR_CHECK(D == MS_D && H == MS_H, "mha_small_fwd: d_model must be 256 with 8 heads");
-    MhaSmallParams p; memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = ldx; p.w_in = w_in; p.b_in = b_in; p.w_out = w_out; p.kpm = kpm; p.qkv = qkv; p.o = o; p.lse = lse; p.ypart = ypart;
-    p.B = B; p.L = L; p.scale = scale; p.p_drop = p_drop; p.seed = seed; p.seed_ptr = seed_ptr;
-    return mha_small_launch(&p, 1, false, stream);
+static int mha_cross_check(const char* what, const MhaCrossParams& p, bool bwd) {
+    LDETR_CHECK(p.Lq >= 1 && p.Lq <= 16 && p.Lk >= 1 && p.Lk <= 64 && p.B >= 0, "%s: 1 <= Lq <= 16 queries and 1 <= Lk <= 64 keys per sample", what);
+    LDETR_CHECK(p.w_q && p.k && p.v && p.w_out && p.q && p.o && p.lse, "%s: null pointer", what);
+    if (!bwd) {
+        LDETR_CHECK(p.x && p.b_q && p.ypart, "%s: null pointer", what);
+        LDETR_CHECK(p.ldx >= MS_D && p.ldx % 4 == 0 && p.ldk % 4 == 0 && p.ldv % 4 == 0, "%s: row pitches must be multiples of 4 floats", what);
+        LDETR_CHECK((((uintptr_t)p.x | (uintptr_t)p.w_q | (uintptr_t)p.w_out | (uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)p.o | (uintptr_t)p.q | (uintptr_t)p.ypart) & 15) == 0,
+                    "%s: buffers must be 16-byte aligned", what);
+    } else {
+        LDETR_CHECK(p.dr && p.dk && p.dv && p.dxpart, "%s: null pointer", what);
+        LDETR_CHECK(p.ldk % 4 == 0 && p.ldv % 4 == 0 && p.lddk % 4 == 0 && p.lddv % 4 == 0, "%s: row pitches must be multiples of 4 floats", what);
+        LDETR_CHECK((((uintptr_t)p.dr | (uintptr_t)p.w_q | (uintptr_t)p.w_out | (uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)p.o | (uintptr_t)p.q | (uintptr_t)p.dq |
+                      (uintptr_t)p.dk | (uintptr_t)p.dv | (uintptr_t)p.dxpart) & 15) == 0, "%s: buffers must be 16-byte aligned", what);
+    }
+    LDETR_CHECK(p.p_drop >= 0.f && p.p_drop < 1.f, "%s: p_drop out of range", what);
+    return LDETR_OK;
 }
 
-extern "C" int ldetr_mha_cross_bwd_f32(const ldetr_mha_cross_args* a, void* stream) {
-    LDETR_CHECK(a != nullptr, "mha_cross_bwd: null argument block");
+static int mha_cross_launch(const ldetr_mha_cross_args* a, bool bwd, void* stream) {
+    const char* what = bwd ? "mha_cross_bwd" : "mha_cross_fwd";
+    LDETR_CHECK(a != nullptr, "%s: null argument block", what);
     const MhaCrossParams& p = *a;
-    LDETR_CHECK(p.Lq >= 1 && p.Lq <= 16 && p.Lk >= 1 && p.Lk <= 64 && p.B >= 0, "mha_cross_bwd: 1 <= Lq <= 16 queries and 1 <= Lk <= 64 keys per sample");
-    LDETR_CHECK(p.dr && p.w_q && p.k && p.v && p.w_out && p.q && p.o && p.lse && p.dk && p.dv && p.dxpart, "mha_cross_bwd: null pointer");
-    LDETR_CHECK(p.ldk % 4 == 0 && p.ldv % 4 == 0 && p.lddk % 4 == 0 && p.lddv % 4 == 0, "mha_cross_bwd: row pitches must be multiples of 4 floats");
-    LDETR_CHECK((((uintptr_t)p.dr | (uintptr_t)p.w_q | (uintptr_t)p.w_out | (uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)p.o | (uintptr_t)p.q | (uintptr_t)p.dq |
-                  (uintptr_t)p.dk | (uintptr_t)p.dv | (uintptr_t)p.dxpart) & 15) == 0, "mha_cross_bwd: buffers must be 16-byte aligned");
-    LDETR_CHECK(p.p_drop >= 0.f && p.p_drop < 1.f, "mha_cross_bwd: p_drop out of range");
+    if (int rc = mha_cross_check(what, p, bwd)) return rc;
     if (p.B == 0) return LDETR_OK;
-    hipLaunchKernelGGL(mha_cross_bwd_kernel, dim3((unsigned)(p.B * MS_H)), dim3(320), 0, (hipStream_t)stream, p);
+    if (bwd) hipLaunchKernelGGL(mha_cross_bwd_kernel, dim3((unsigned)(p.B * MS_H)), dim3(320), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(mha_cross_fwd_kernel, dim3((unsigned)(p.B * MS_H)), dim3(256), 0, (hipStream_t)stream, p);
     note_engine_launch(false);
-    return check_launch("mha_cross_bwd");
+    return check_launch(what);
 }
+
+extern "C" int ldetr_mha_cross_fwd_f32(const ldetr_mha_cross_args* a, void* stream) { return mha_cross_launch(a, false, stream); }
+extern "C" int ldetr_mha_cross_bwd_f32(const ldetr_mha_cross_args* a, void* stream) { return mha_cross_launch(a, true, stream); }
 
 extern "C" int ldetr_wgrad_multi_f32(const ldetr_wgrad_desc* d, int n, void* stream) {
     LDETR_CHECK(d && n >= 1 && n <= 8, "wgrad_multi: 1..8 problems");
@@ -901,26 +908,4 @@ extern "C" int ldetr_wgrad_multi_f32(const ldetr_wgrad_desc* d, int n, void* str
     hipLaunchKernelGGL(wgrad_multi_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, m);
     note_engine_launch(false);
     return check_launch("wgrad_multi");
-}
-
-extern "C" int ldetr_mha_cross_fwd_f32(const float* x, int64_t ldx, const float* w_q, const float* b_q,
-                                       const float* k, int64_t ldk, const float* v, int64_t ldv, const float* w_out,
-                                       const uint8_t* kpm, float* q, float* o, float* lse, float* ypart,
-                                       int B, int Lq, int Lk, int D, int H, float scale, float p_drop, uint64_t seed, const uint64_t* seed_ptr,
-                                       void* stream) {
-    LDETR_CHECK(D == MS_D && H == MS_H, "mha_cross_fwd: d_model must be 256 with 8 heads");
-    LDETR_CHECK(Lq >= 1 && Lq <= 16 && Lk >= 1 && Lk <= 64 && B >= 0, "mha_cross_fwd: 1 <= Lq <= 16 queries and 1 <= Lk <= 64 keys per sample");
-    LDETR_CHECK(x && w_q && b_q && k && v && w_out && q && o && lse && ypart, "mha_cross_fwd: null pointer");
-    LDETR_CHECK(ldx >= MS_D && ldx % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "mha_cross_fwd: row pitches must be multiples of 4 floats");
-    LDETR_CHECK((((uintptr_t)x | (uintptr_t)w_q | (uintptr_t)w_out | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)q | (uintptr_t)ypart) & 15) == 0,
-                "mha_cross_fwd: buffers must be 16-byte aligned");
-    LDETR_CHECK(p_drop >= 0.f && p_drop < 1.f, "mha_cross_fwd: p_drop out of range");
-    if (B == 0) return LDETR_OK;
-    MhaCrossParams p; memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = ldx; p.w_q = w_q; p.b_q = b_q; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv; p.w_out = w_out; p.kpm = kpm;
-    p.q = q; p.o = o; p.lse = lse; p.ypart = ypart; p.B = B; p.Lq = Lq; p.Lk = Lk; p.scale = scale; p.p_drop = p_drop;
-    p.seed = seed; p.seed_ptr = seed_ptr;
-    hipLaunchKernelGGL(mha_cross_fwd_kernel, dim3((unsigned)(B * MS_H)), dim3(256), 0, (hipStream_t)stream, p);
-    note_engine_launch(false);
-    return check_launch("mha_cross_fwd");
 }

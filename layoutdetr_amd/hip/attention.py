@@ -100,7 +100,7 @@ class _AttnPackedFn(torch.autograd.Function):
         return dqkv, (None if v_sep is None else dv), None, None, None, None, None, None
 
 
-def _kpm_u8(key_padding_mask):
+def kpm_u8(key_padding_mask):
     """bool / uint8 key-padding mask -> contiguous uint8 (a contiguous bool mask is reinterpreted in place: one byte per element holding 0 / 1)."""
     m = key_padding_mask
     if m is None:
@@ -111,7 +111,7 @@ def _kpm_u8(key_padding_mask):
 
 
 def attention(q, k, v, key_padding_mask, B, H, Lq, Lk, p_drop=0.0, kv_grad_dst=None):
-    return _AttnFn.apply(q, k, v, _kpm_u8(key_padding_mask), B, H, Lq, Lk, p_drop, kv_grad_dst)
+    return _AttnFn.apply(q, k, v, kpm_u8(key_padding_mask), B, H, Lq, Lk, p_drop, kv_grad_dst)
 
 
 class _GroupedKVFn(torch.autograd.Function):
@@ -245,19 +245,19 @@ def mha_forward(query, key, value, in_proj_weight, in_proj_bias, out_w, out_b, n
     if same_qkv:
         r = linear(query, W, bvec, passthru=passthru)
         qkv, alias = r if passthru else (r, query)
-        o = _AttnPackedFn.apply(qkv, None, _kpm_u8(key_padding_mask), B, nhead, Lq, p_drop)
+        o = _AttnPackedFn.apply(qkv, None, kpm_u8(key_padding_mask), B, nhead, Lq, p_drop)
     elif same_qk and qk_in is not None:
         qk = linear(qk_in, W, bvec, rows=(0, 2 * d))
         r = linear(query, W, bvec, rows=(2 * d, 3 * d), passthru=passthru)
         v, alias = r if passthru else (r, query)
-        o = _AttnPackedFn.apply(qk, v, _kpm_u8(key_padding_mask), B, nhead, Lq, p_drop)
+        o = _AttnPackedFn.apply(qk, v, kpm_u8(key_padding_mask), B, nhead, Lq, p_drop)
     elif same_qk:
         r = linear(query, W, bvec, rows=(0, 2 * d), add_input=qk_pos, passthru=passthru)
         qk, alias = r if passthru else (r, query)
         vin = alias if value is query else value
         r = linear(vin, W, bvec, rows=(2 * d, 3 * d), passthru=passthru and value is query)
         v, alias = r if (passthru and value is query) else (r, alias)
-        o = _AttnPackedFn.apply(qk, v, _kpm_u8(key_padding_mask), B, nhead, Lq, p_drop)
+        o = _AttnPackedFn.apply(qk, v, kpm_u8(key_padding_mask), B, nhead, Lq, p_drop)
     else:
         r = linear(query, W, bvec, rows=(0, d), passthru=passthru)
         q, alias = r if passthru else (r, query)

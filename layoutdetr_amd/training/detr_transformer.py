@@ -14,6 +14,7 @@ import torch
 from torch import Tensor, nn
 
 from ..hip import composite, core
+from ..hip.attention import kpm_u8 as _mask_u8      # bool key-padding mask -> the uint8 form the attention kernels read (no launch for a contiguous mask)
 from ..hip.attention import grouped_kv, mha_cross_kv, mha_forward
 from ..hip import ffn as hffn
 from ..hip import stacks as hstacks
@@ -38,15 +39,6 @@ def _mha(m: nn.MultiheadAttention, q2, k2, v2, B, Lq, Lk, kpm, training, same_qk
 
 _GROUP_KV = True
 
-def _mask_u8(kpm):
-    """bool key-padding mask -> the uint8 form the attention kernels read: a torch.bool tensor is one byte per element holding 0 / 1, so a
-    contiguous mask is reinterpreted in place (no launch); only a strided one is copied."""
-    if kpm is None or kpm.dtype == torch.uint8:
-        return kpm
-    if kpm.dtype == torch.bool:
-        return (kpm if kpm.is_contiguous() else kpm.contiguous()).view(torch.uint8)
-    return kpm.to(torch.uint8).contiguous()
-
 
 def _ffn(layer, x2):
     """-> (FFN output, alias of x2 for the residual branch)."""
@@ -57,19 +49,19 @@ def _ffn(layer, x2):
     return linear(h, layer.linear2.weight, layer.linear2.bias), x2
 
 
-def _add_ln(norm: nn.LayerNorm, x2, r2, drop: nn.Dropout, training, pos=None, r_bias=None):
-    return add_layernorm(x2, r2, norm.weight, norm.bias, norm.eps, drop.p if training else 0.0, pos=pos, r_bias=r_bias)
+def _add_ln(norm: nn.LayerNorm, x2, r2, drop: nn.Dropout, training, pos=None):
+    return add_layernorm(x2, r2, norm.weight, norm.bias, norm.eps, drop.p if training else 0.0, pos=pos)
 
 
-def _add_ln_ffn_add_ln(layer, norm_a: nn.LayerNorm, x2, r2, drop_a: nn.Dropout, norm_b: nn.LayerNorm, drop_b: nn.Dropout, pos=None, r_bias=None):
+def _add_ln_ffn_add_ln(layer, norm_a: nn.LayerNorm, x2, r2, drop_a: nn.Dropout, norm_b: nn.LayerNorm, drop_b: nn.Dropout, pos=None):
     """The tail of a layer: x1 = norm_a(x + dropout(r)); norm_b(x1 + dropout(linear2(dropout(relu(linear1(x1)))))) (detr_transformer.py:210-214
     / 280-285).  On the token counts of the decoder-side stacks ONE autograd node of 3 launches forward / 4 backward (hip/ffn.py: fused
     feed-forward launch, its partial sums reduced inside the LayerNorm launches); otherwise LayerNorm, two GEMMs, LayerNorm."""
     t = layer.training
     if hffn.usable(x2, layer.linear1, layer.linear2):
         return hffn.add_ln_ffn_add_ln(x2, r2, norm_a, drop_a.p if t else 0.0, layer.linear1, layer.linear2, norm_b, layer.dropout.p if t else 0.0,
-                                      drop_b.p if t else 0.0, pos=pos, r_bias=r_bias)
-    x2 = _add_ln(norm_a, x2, r2, drop_a, t, r_bias=r_bias)
+                                      drop_b.p if t else 0.0, pos=pos)
+    x2 = _add_ln(norm_a, x2, r2, drop_a, t)
     f, x2 = _ffn(layer, x2)
     return _add_ln(norm_b, x2, f, drop_b, t, pos=pos)
 

@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f'{name} declared in include/ldetr_hip.h but not exported'
     assert declared - {'ldetr_last_error', 'ldetr_abi_version'} == set(_lib.SIGNATURES), 'ctypes table out of sync with the header'
-    assert lib.ldetr_abi_version() == _lib.ABI_VERSION == 24
+    assert lib.ldetr_abi_version() == _lib.ABI_VERSION == 25
 
 
 def test_no_cpu_fallback():
@@ -59,6 +59,59 @@ def test_argument_validation_without_gpu():
     rc = lib.ldetr_lsap_f64(ctypes.c_void_p(8), 1, 99, 0, ctypes.c_void_p(8), ctypes.c_void_p(8), None)
     assert rc != 0 and b'n must be' in lib.ldetr_last_error()
     assert lib.ldetr_bias_act_f32(None, None, None, None, None, None, 0, 0, 1, 0, 3, 0.2, 1.0, -1.0, None) == 0  # empty input
+
+
+_GROUP_ENTRIES = [('ldetr_layernorm_fwd_group_f32', 'LnArgs', b'layernorm_fwd_group: 1 or 2 problems'),
+                  ('ldetr_layernorm_bwd_group_f32', 'LnArgs', b'layernorm_bwd_group: 1 or 2 problems'),
+                  ('ldetr_ffn_fwd_group_f32', 'FfnArgs', b'ffn_fwd: 1 or 2 problems'),
+                  ('ldetr_ffn_bwd_group_f32', 'FfnArgs', b'ffn_bwd: 1 or 2 problems'),
+                  ('ldetr_mha_small_fwd_group_f32', 'MhaSmallArgs', b'mha_small_fwd: 1 or 2 problems'),
+                  ('ldetr_mha_small_bwd_group_f32', 'MhaSmallArgs', b'mha_small_bwd: 1 or 2 problems')]
+
+
+@pytest.mark.parametrize('entry,struct,message', _GROUP_ENTRIES)
+def test_group_entries_reject_bad_problem_counts_and_null_blocks(entry, struct, message):
+    """The argument-block entries of the token-block kernels take 1 or 2 problems: n = 0, n = 3 and a NULL block return before any launch."""
+    from layoutdetr_amd import _lib
+    lib = _lib.load()
+    fn = getattr(lib, entry)
+    arr = (getattr(_lib, struct) * 3)()
+    for a, n in ((arr, 0), (arr, 3), (None, 1)):
+        rc = fn(a, n, None)
+        assert rc != 0 and lib.ldetr_last_error() == message, (a is None, n, lib.ldetr_last_error())
+
+
+@pytest.mark.parametrize('direction', ['fwd', 'bwd'])
+def test_cross_attention_entries_validate_their_argument_block(direction):
+    """ldetr_mha_cross_{fwd,bwd}_f32 take the same argument block and check it before any launch (B = 0 here: even an accepted block launches
+    nothing)."""
+    import ctypes
+    from layoutdetr_amd import _lib
+    lib = _lib.load()
+    fn = getattr(lib, f'ldetr_mha_cross_{direction}_f32')
+    what = f'mha_cross_{direction}: '.encode()
+    buf = ctypes.create_string_buffer(64)
+    p = (ctypes.addressof(buf) + 15) & ~15      # any non-NULL 16-byte aligned address: nothing is dereferenced on the host
+
+    def block(**changes):
+        a = _lib.MhaCrossArgs()
+        for name, ctype in a._fields_:
+            if ctype is ctypes.c_void_p and name not in ('kpm', 'seed_ptr'):
+                setattr(a, name, p)
+        a.ldx = a.ldk = a.ldv = a.lddk = a.lddv = 256
+        a.B, a.Lq, a.Lk, a.scale, a.p_drop = 0, 9, 37, 0.25, 0.1
+        for k, v in changes.items():
+            setattr(a, k, v)
+        return ctypes.byref(a)
+    assert fn(block(), None) == 0
+    rc = fn(None, None)
+    assert rc != 0 and lib.ldetr_last_error() == what + b'null argument block'
+    for changes, message in [(dict(Lq=17), b'1 <= Lq <= 16 queries and 1 <= Lk <= 64 keys per sample'),
+                             (dict(Lk=65), b'1 <= Lq <= 16 queries and 1 <= Lk <= 64 keys per sample'),
+                             (dict(ldk=258), b'row pitches must be multiples of 4 floats'),
+                             (dict(p_drop=1.0), b'p_drop out of range')]:
+        rc = fn(block(**changes), None)
+        assert rc != 0 and lib.ldetr_last_error() == what + message, (changes, lib.ldetr_last_error())
 
 
 def test_layout_losses_and_position_encoding_match_reference_golden():

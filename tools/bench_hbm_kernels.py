@@ -62,7 +62,7 @@ def measure_named(B=16):
     the fused modulated-conv layer at 256x256) and MFMA utilisation of DETR cross-attention, in-kernel and device-level."""
     import math
     from layoutdetr_amd.hip import attention as hattn
-    from layoutdetr_amd.hip import core, modconv
+    from layoutdetr_amd.hip import blocks, core, modconv
     dev = torch.device('cuda')
     HBM, MFMA = 8.0, 157.3
     out = []
@@ -121,16 +121,15 @@ def measure_named(B=16):
     x = torch.randn(B * Lq, d, device=dev)
     qb = torch.empty(B * Lq, d, device=dev); ob = torch.empty(B * Lq, d, device=dev); lse = torch.empty(B * H * Lq, device=dev); yp = torch.empty(H, B * Lq, d, device=dev)
     qkv = torch.empty(B * Lq, 3 * d, device=dev)
-    L = core.lib()
-    t = timed(lambda: core.check(L.ldetr_mha_cross_fwd_f32(core.ptr(x), d, core.ptr(Wi), core.ptr(bi), core.ptr(k), d, core.ptr(v), d, core.ptr(Wo), None, core.ptr(qb), core.ptr(ob),
-                                                           core.ptr(lse), core.ptr(yp), B, Lq, S, d, H, 1.0 / dh ** 0.5, 0.0, 0, None, core.stream())))
+    cross = [blocks.mha_cross_fwd(x, Wi, bi, k, v, Wo, None, qb, ob, lse, yp, B, Lq, S, 0.0, 0)]
+    t = timed(lambda: blocks.launch('mha_cross_fwd', cross))
     fl2 = 2.0 * B * Lq * d * d * 2 + fl
     cyc = (128 // 4 + 2 * (S // 16) * (dh // 4) + 128 // 4) * 32          # per-SIMD MFMA issue cycles of a (sample, head) block: projection, attention (one wave), output projection
     out.append(dict(kernel='DETR cross-attention sub-block fwd (mha_cross_fwd_kernel: q projection + attention + out projection)', shape=f'(b*h={B * H}, Lq={Lq}, Lk={S}, dh={dh})', bound='latency',
                     achieved=round(fl2 / t / 1e12, 4), peak=MFMA, unit='TFLOP/s', frac=round(fl2 / t / 1e12 / MFMA, 6), us=round(t * 1e6, 2), mfma_util_device=round(fl2 / t / 1e12 / MFMA, 6),
                     mfma_util_in_kernel=round(cyc / (t * 2.4e9), 4), note='replaces three launches (5.5 + 8.9 + 5.5 us stand-alone); rows 10..15 of every 16-row MFMA tile are padding'))
-    t = timed(lambda: core.check(L.ldetr_mha_small_fwd_f32(core.ptr(x), d, core.ptr(Wi), core.ptr(bi), core.ptr(Wo), None, core.ptr(qkv), core.ptr(ob), core.ptr(lse), core.ptr(yp),
-                                                           B, Lq, d, H, 1.0 / dh ** 0.5, 0.0, 0, None, core.stream())))
+    small = [blocks.mha_small_fwd(x, Wi, bi, Wo, None, qkv, ob, lse, yp, B, Lq, 0.0, 0)]
+    t = timed(lambda: blocks.launch('mha_small_fwd', small))
     fl3 = 2.0 * B * Lq * d * (3 * d) + 4.0 * Lq * Lq * dh * B * H + 2.0 * B * Lq * d * d
     out.append(dict(kernel='self-attention sub-block fwd (mha_small_fwd_kernel: packed projection + attention + out projection)', shape=f'(b*h={B * H}, L={Lq}, dh={dh})', bound='latency',
                     achieved=round(fl3 / t / 1e12, 4), peak=MFMA, unit='TFLOP/s', frac=round(fl3 / t / 1e12 / MFMA, 6), us=round(t * 1e6, 2),
