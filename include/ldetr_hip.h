@@ -30,6 +30,8 @@
  *                                 layouts: generate.py:88-136,309-329, generate_util.py:100-148,424-450
  *   ldetr_resample_coeffs, ldetr_resize_normalize_u8
  *                                 PIL resize + normalise of the page background: training/dataset_layoutganpp.py:330-338
+ *   ldetr_resample_coeffs_filter, ldetr_layout_raster_cell_size, ldetr_layout_raster_u8
+ *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
  *   ldetr_lsap_f64                scipy.optimize.linear_sum_assignment as used at metrics/metric_layoutnet.py:111,125,240
  *   ldetr_layoutnet_features_f32  LayoutNet.extract_features, the feature network of the layout FID: training/networks_layoutnet.py:48-66
  *   ldetr_feature_stats_f64       FeatureStats.append with capture_mean_cov: metrics/metric_utils_layout.py:97-112
@@ -419,6 +421,42 @@ int ldetr_layout_losses_bwd_f32(const float* grads, const float* grad_losses, in
  * indices in stable ascending order of overlap[c], NaN last.  C * K == 0 returns 0 without touching a pointer. */
 int ldetr_layout_finish_f32(const float* bbox_in, const int* num, const float* factors, const unsigned char* jitter, const unsigned char* mode,
                             float* bbox_out, float* overlap, float* alignment, int* order, int C, int K, int N, void* stream);
+
+/* Snapshot grids of layouts (util.py:85-141: convert_layout_to_image, expand2square, save_image's ToTensor / make_grid / save_image), one launch per
+ * grid, bit-identical to the reference's PNG pixels (csrc/layout_raster.hip; the rule is DESIGN.md section 13).
+ * ldetr_resample_coeffs_filter (HOST memory, no GPU work): ldetr_resample_coeffs with the window chosen, LDETR_FILTER_BILINEAR (Pillow's triangle
+ * window, util.py:111) or LDETR_FILTER_LANCZOS (what ldetr_resample_coeffs computes).
+ * ldetr_layout_raster_cell_size (HOST): the size a W x H page is resized to inside an S x S cell (util.py:105-110, double arithmetic).
+ * ldetr_layout_raster_u8: cell b draws the valid boxes of bbox[b] over a white page (page_index[b] == -1 or n_pages == 0) or over page
+ * page_index[b] of the page table, resizes it and writes it letterboxed at its place in the grid `out` [Hg][Wg][3]: B == 1 gives the S x S cell
+ * itself, otherwise make_grid's layout with xmaps = min(nrow, B) columns (nrow <= 0: ceil(sqrt(B))) and 2 pixels of zero padding.  Arrays marked
+ * HOST are read on the host only; the entry validates them (N <= 16, S even, resized sizes >= 1, page table against pages_bytes and page_wh,
+ * coefficient tables against coeffs_len, labels of valid slots against the palette) before it uploads one descriptor per cell to cells_dev and
+ * launches.  B == 0 returns 0. */
+#define LDETR_FILTER_BILINEAR 0
+#define LDETR_FILTER_LANCZOS 1
+typedef struct ldetr_layout_raster_args {
+    int struct_bytes;             /* sizeof(ldetr_layout_raster_args) as the caller sees it */
+    int B, N, S, nrow, n_colors, n_pages;
+    const float* bbox;            /* device [B][N][4] (xc, yc, w, h) */
+    const uint8_t* valid;         /* HOST [B][N], non-zero = draw the slot */
+    const int32_t* labels;        /* HOST [B][N] */
+    const uint8_t* palette;       /* HOST [n_colors][3] RGB */
+    const int32_t* page_wh;       /* HOST [B][2] = (W, H) of each cell's page */
+    const uint8_t* pages;         /* device, pages_bytes bytes: uint8 [H][W][3] pages at the table's offsets (NULL when n_pages == 0) */
+    int64_t pages_bytes;
+    const int64_t* page_table;    /* HOST [n_pages][3] = (byte offset, W, H) */
+    const int32_t* page_index;    /* HOST [B]: row of the page table, -1 = white page; several cells may name one page */
+    const int32_t* coeffs;        /* device pool of int32: per table bounds [out][2] followed by weights [ksize][out] (ldetr_resample_coeffs_filter, bilinear) */
+    int64_t coeffs_len;
+    const int64_t* cell_coeffs;   /* HOST [B][4] = (offset of the W -> Wn table in the pool, its ksize, offset of the H -> Hn table, its ksize); offset -1 for a
+                                     pass whose sizes agree (it is skipped) */
+    int32_t* cells_dev;           /* device scratch, B * 32 int32 */
+    uint8_t* out;                 /* device [Hg][Wg][3] */
+} ldetr_layout_raster_args;
+int ldetr_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t* bounds, int32_t* weights, int64_t weights_capacity, int* ksize_out);
+int ldetr_layout_raster_cell_size(int W, int H, int S, int* wn_out, int* hn_out);
+int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* stream);
 
 /* Batched linear-sum-assignment (Hungarian / shortest augmenting path) on device.
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;

@@ -78,6 +78,14 @@ class WgradDesc(Structure):
                 ('M', c_int), ('rows', c_int), ('cols', c_int)]
 
 
+class LayoutRasterArgs(Structure):
+    """ldetr_layout_raster_args."""
+    _fields_ = [('struct_bytes', c_int), ('B', c_int), ('N', c_int), ('S', c_int), ('nrow', c_int), ('n_colors', c_int), ('n_pages', c_int),
+                ('bbox', c_void_p), ('valid', c_void_p), ('labels', c_void_p), ('palette', c_void_p), ('page_wh', c_void_p),
+                ('pages', c_void_p), ('pages_bytes', c_int64), ('page_table', c_void_p), ('page_index', c_void_p),
+                ('coeffs', c_void_p), ('coeffs_len', c_int64), ('cell_coeffs', c_void_p), ('cells_dev', c_void_p), ('out', c_void_p)]
+
+
 _P = c_void_p
 _I = c_int
 _L = c_int64
@@ -147,6 +155,9 @@ SIGNATURES = {
     'ldetr_layout_losses_bwd_f32': [_P, _P, _I, _I, _P, _P],
     'ldetr_layout_finish_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     'ldetr_resample_coeffs': [_I, _I, _P, _P, _L, _P],
+    'ldetr_resample_coeffs_filter': [_I, _I, _I, _P, _P, _L, _P],
+    'ldetr_layout_raster_cell_size': [_I, _I, _I, _P, _P],
+    'ldetr_layout_raster_u8': [_P, _P],
     'ldetr_p3_split_f32': [_P, _L, _P, _L, _I, _P],
     'ldetr_p3_merge_f32': [_P, _P, _L, _L, _I, _P],
     'ldetr_p3_weight_bwd': [_P, _P, _P, _I, _I, _I, _I, _P],

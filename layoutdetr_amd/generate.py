@@ -125,6 +125,26 @@ class Layouts(object):
         self.bbox_raw, self.bbox, self.overlap, self.alignment, self.order = bbox_raw, bbox, overlap, alignment, order
         self.num, self.jitter, self.modes, self.seeds = num, jitter, modes, seeds
 
+    def sheet(self, page_u8, labels, canvas=256, nrow=None, condition=0):
+        """Contact sheet of one condition: its K candidates in rank order (best first), each drawn over the page, as ONE raster launch with one
+        shared page (render.layout_grid: the drawing rule of the training snapshots, this module's palette).  page_u8: uint8 [H, W, 3];
+        labels: the condition's label indices, one per element.  -> uint8 [Hg, Wg, 3] on the boxes' device."""
+        from . import render
+        labels = [int(l) % len(PALETTE) for l in labels]
+        n = len(labels)
+        if not 1 <= n <= N_SLOTS:
+            raise ValueError(f'sheet: 1..{N_SLOTS} labels, one per element')
+        dev = self.bbox.device
+        K = self.bbox.shape[1]
+        boxes = self.bbox[condition].index_select(0, self.order[condition].long())          # rank order, no host round trip
+        valid = (torch.arange(N_SLOTS) < n).expand(K, N_SLOTS)
+        lab = torch.tensor(labels + [0] * (N_SLOTS - n), dtype=torch.int32).expand(K, N_SLOTS)
+        page = torch.as_tensor(page_u8).to(dev)
+        if page.dtype != torch.uint8 or page.ndim != 3 or page.shape[2] != 3:
+            raise ValueError('sheet: the page must be uint8 [H, W, 3]')
+        return render.layout_grid(boxes, valid, lab, PALETTE, (int(page.shape[1]), int(page.shape[0])), pages=render.PageSet(page),
+                                  page_index=[0] * K, canvas=canvas, nrow=nrow)
+
 
 def _plan_arrays(K, jitter, modes):
     j = [False] * K if jitter is None else [bool(v) for v in jitter]
@@ -236,6 +256,7 @@ def build_parser():
     p.add_argument('--out-postprocessing', default='none', choices=sorted(MODE_NAMES))
     p.add_argument('--out-jittering-strength', type=float, default=0.0)
     p.add_argument('--vocab', default=None, help='bert-base-uncased vocab.txt when the snapshot does not carry a tokenizer (or set LDETR_BERT_VOCAB)')
+    p.add_argument('--sheet', action='store_true', help='also write <outfile>_sheet.png: every candidate over the page, in rank order')
     p.add_argument('--outfile', required=True)
     return p
 
@@ -303,7 +324,10 @@ def main(argv=None):
     with open(a.outfile + '.json', 'w') as f:
         json.dump(out, f, indent=1)
     draw_boxes(page, res.bbox[0, order[0], :n].tolist(), a.labels, a.outfile + '_bboxes.png')
-    print(f'wrote {a.outfile}.json and {a.outfile}_bboxes.png (best candidate: seed {a.seeds[order[0]]}, overlap {out["overlap"][order[0]]:.4f})')
+    if a.sheet:
+        from . import render
+        render.save_png(res.sheet(torch.from_numpy(np.array(page)), a.labels), a.outfile + '_sheet.png')
+    print(f'wrote {a.outfile}.json and {a.outfile}_bboxes.png' + (f' and {a.outfile}_sheet.png' if a.sheet else '') + f' (best candidate: seed {a.seeds[order[0]]}, overlap {out["overlap"][order[0]]:.4f})')
 
 
 if __name__ == '__main__':

@@ -888,8 +888,12 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     layout FID, overlap / alignment / layout-wise IoU / DocSim, `_train` on the training set, `_val` on the validation set).  Their results go to
     `metric-<name>.jsonl`, into the next `stats.jsonl` line as `Metrics/<key>` and into the returned dict; an evaluation (calc_metric) leaves G_ema and the torch /
     numpy generator states as it found them, so training does not depend on whether metrics ran.  A metric this package does not register (the
-    image metrics: `train.py`'s default `fid50k_full`) is skipped with one printed note.  NOT done here (a note is printed): augment pipe, ADA,
-    image snapshots, tensorboard — SURVEY §8 marks them outside the hot path.
+    image metrics: `train.py`'s default `fid50k_full`) is skipped with one printed note.  Image snapshots (:209-223, :371-392) on rank 0 when
+    `image_snapshot_ticks` is not None: `train_layouts_real.png` / `val_layouts_real.png` at start and `*_layouts_fake_<kimg>.png` of G_ema on the fixed
+    samples and a private fixed z every `image_snapshot_ticks` ticks and at the end, pixels as the reference's save_image writes them, plus this package's
+    `*_layouts_over_background_*` (the boxes over the decoded page), one raster launch per grid (training/snapshot_images.py, render.py); like the metrics
+    they leave G_ema and the generator states as found, and a dataset without page sizes or palette is skipped with one printed note.  NOT done here (a
+    note is printed): augment pipe, ADA, the `*_images_*` snapshot kinds (they paste decoded text patches; this path never decodes patches), tensorboard.
     Returns dict(stats of the last tick, G, D, G_ema, snapshot_pkl, metrics)."""
     import json
     import os
@@ -940,7 +944,12 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     dp = DataParallelStep(world_size=num_gpus)
     ema = EmaTracker(phases[0], G_ema)
     if rank == 0:
-        print('Not run on this path: augment pipe, ADA, image snapshots (outside the hot path)')
+        print('Not run on this path: augment pipe, ADA, the *_images_* snapshot kinds (text patches are never decoded here), tensorboard')
+    image_snapshots = None
+    if rank == 0 and image_snapshot_ticks is not None and run_dir and os.path.isdir(run_dir):      # :148-150, :209-223
+        from .snapshot_images import ImageSnapshots
+        image_snapshots = ImageSnapshots.setup(run_dir, training_set_kwargs, validation_set_kwargs, G, batch_size, batch_gpu, device)
+    if rank == 0:
         print(f'Training for {total_kimg} kimg...')
     cur_nimg, cur_tick, tick_start_nimg, tick_start = resume_kimg * 1000, 0, resume_kimg * 1000, time.time()
     batch_idx = 0
@@ -988,6 +997,9 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
         pending_metrics = {}
         if abort_fn is not None and abort_fn():
             done = True
+        # :371-392: image snapshot of G_ema on the fixed grid samples
+        if image_snapshots is not None and (done or cur_tick % image_snapshot_ticks == 0):
+            image_snapshots.write_fake(G_ema, cur_nimg)
         # :395-412: network snapshot (every `network_snapshot_ticks` ticks and at the end), consistency-checked across ranks
         if network_snapshot_ticks is not None and (done or cur_tick % network_snapshot_ticks == 0) and run_dir and os.path.isdir(run_dir):
             snapshot_pkl = os.path.join(run_dir, f'network-snapshot-{cur_nimg // 1000:06d}.pkl')
