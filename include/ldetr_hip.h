@@ -30,6 +30,8 @@
  *                                 layouts: generate.py:88-136,309-329, generate_util.py:100-148,424-450
  *   ldetr_resample_coeffs, ldetr_resize_normalize_u8
  *                                 PIL resize + normalise of the page background: training/dataset_layoutganpp.py:330-338
+ *   ldetr_page_filter_u8          ImageFilter.GaussianBlur / convert('L').filter(FIND_EDGES).convert('RGB') of the page background:
+ *                                 generate.py:267-269, 280-282
  *   ldetr_resample_coeffs_filter, ldetr_layout_raster_cell_size, ldetr_layout_raster_u8
  *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
  *   ldetr_lsap_f64                scipy.optimize.linear_sum_assignment as used at metrics/metric_layoutnet.py:111,125,240
@@ -389,6 +391,14 @@ int ldetr_resize_normalize_u8(const uint8_t* src, int64_t images, int H, int W, 
                               const int32_t* hweights, int hksize, const int32_t* vbounds, const int32_t* vweights, int vksize,
                               uint8_t* tmp, uint8_t* out_u8, float* out_chw, float mean0, float mean1, float mean2, float std0,
                               float std1, float std2, void* stream);
+
+/* The page filters of generate.py's --bg-preprocessing (generate.py:267-269, 280-282), applied to decoded uint8 RGB pages before the resize; Pillow's
+ * 8-bit arithmetic, bit-identical (csrc/page_filter.hip).  src, dst: [images][H][W][3] uint8 in device memory, 4-byte aligned, not overlapping.
+ * kind LDETR_PAGE_FILTER_BLUR: ImageFilter.GaussianBlur(radius), 0 < radius <= 5 (three box passes along x, three along y, each rounded to 8 bits);
+ * kind LDETR_PAGE_FILTER_EDGE: convert('L').filter(FIND_EDGES).convert('RGB'), radius ignored.  One launch per call; images == 0 is a no-op. */
+#define LDETR_PAGE_FILTER_BLUR 1
+#define LDETR_PAGE_FILTER_EDGE 2
+int ldetr_page_filter_u8(const uint8_t* src, uint8_t* dst, int64_t images, int H, int W, int kind, float radius, void* stream);
 
 /* Demodulation coefficients of the modulated convolution (training/networks_stylegan2.py:57-61), forward and backward:
  * dcoefs[b][o] = rsqrt(sum_{i,kh,kw} (weight[o][i][kh][kw] * styles[b][i])^2 + eps).  weight is addressed through its element

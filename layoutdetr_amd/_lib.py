@@ -171,6 +171,7 @@ SIGNATURES = {
     'ldetr_engine_last_launch': [_P],
     'ldetr_struct_sizes': [_P],
     'ldetr_resize_normalize_u8': [_P, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P],
+    'ldetr_page_filter_u8': [_P, _P, _L, _I, _I, _I, _F, _P],
 }
 
 _lib = None

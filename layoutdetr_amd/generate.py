@@ -27,6 +27,8 @@ N_SLOTS = 9
 MAX_CANDIDATES = 1024
 # element types in label-index order (generate.py's label2index)
 LABEL_LIST = ['header', 'pre-header', 'post-header', 'body', 'disclaimer / footnote', 'button', 'callout', 'logo']
+# --bg-preprocessing, the reference's eight choices (generate.py:214)
+BG_MODES = ['256', '128', 'blur', 'jpeg', 'rec', '3x_mask', 'edge', 'none']
 # one colour per label for the box overlay (this package's own fixed palette)
 PALETTE = [(230, 57, 70), (244, 162, 97), (233, 196, 106), (42, 157, 143), (38, 70, 83), (69, 123, 157), (131, 56, 236), (106, 153, 78)]
 
@@ -90,6 +92,28 @@ def parse_labels(s):
             raise ValueError(f'unknown label {n!r}: one of {LABEL_LIST}')
         out.append(LABEL_LIST.index(n))
     return out
+
+
+def resolve_background(bg, mode):
+    """(background path, --bg-preprocessing mode) -> (path of the image the model sees, page_filter, size it is resized to), generate.py:263-284:
+    '256' / '128' resize the page to that size instead of 1024; 'blur' / 'edge' filter the page on the device (filter_pages) before the resize
+    to 1024; 'jpeg' reads <dir>_jpeg/<name with .png -> .jpg> and 'rec' <dir>_rec/<name>, siblings of the page's directory (:270-279; a bare
+    file name counts as lying in the current directory); '3x_mask' and 'none' take the page as it is.  A missing sibling file is an error
+    that names the path looked for.  No GPU work."""
+    if mode not in BG_MODES:
+        raise ValueError(f'unknown background preprocessing {mode!r}: one of {BG_MODES}')
+    if mode in ('256', '128'):
+        return bg, None, int(mode)
+    if mode in ('blur', 'edge'):
+        return bg, mode, 1024
+    if mode in ('jpeg', 'rec'):
+        d, name = os.path.split(bg)
+        d = (d or os.getcwd()).rstrip('/')
+        path = os.path.join(d + '_' + mode, name.replace('.png', '.jpg') if mode == 'jpeg' else name)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"--bg-preprocessing {mode}: {path} not found (the {mode} version of {bg} is looked for in the sibling directory '<dir>_{mode}')")
+        return path, None, 1024
+    return bg, None, 1024
 
 
 def layout_finish(bbox, num, factors=None, jitter=None, modes=None):
@@ -164,20 +188,23 @@ class Sampler(object):
     def device(self):
         return next(self.G.parameters()).device
 
-    def encode(self, background, texts_or_features, labels, padding_mask=None, background_size=None):
+    def encode(self, background, texts_or_features, labels, padding_mask=None, background_size=None, page_filter=None):
         """background: [C, 3, S, S] normalised fp32, or uint8 pages [C, H, W, 3] / a list of [H, W, 3] pages of any size (resized to
         `background_size`, default 1024 as generate.py:284, and normalised on the device).  texts_or_features: per condition a list of up to 9
         strings (needs the module's tokenizer), or TextTokens / TextFeatures already padded to 9 slots.  labels: per condition a list of label
-        indices, or a [C, 9] tensor.  padding_mask ([C, 9] bool, True = padded) defaults to the prefix mask of the list lengths."""
+        indices, or a [C, 9] tensor.  padding_mask ([C, 9] bool, True = padded) defaults to the prefix mask of the list lengths.
+        page_filter ('blur' / 'edge', uint8 pages only): the pages are filtered on the device before the resize (generate.py:267-269, 280-282)."""
         from .training.dataset_layoutganpp import background_to_tensor
         from .training.shared_decode import check_prefix_mask
         if padding_mask is not None:
             check_prefix_mask(torch.as_tensor(padding_mask))
         dev = self.device
         if isinstance(background, (list, tuple)):
-            background = torch.stack([background_to_tensor(torch.as_tensor(p).to(dev), background_size or 1024) for p in background])
+            background = torch.stack([background_to_tensor(torch.as_tensor(p).to(dev), background_size or 1024, page_filter=page_filter) for p in background])
         elif background.dtype == torch.uint8:
-            background = background_to_tensor(background.to(dev), background_size or 1024)
+            background = background_to_tensor(background.to(dev), background_size or 1024, page_filter=page_filter)
+        elif page_filter is not None:
+            raise ValueError('encode: page_filter needs uint8 pages, not an already normalised background')
         background = background.to(device=dev, dtype=torch.float32)
         C = background.shape[0]
         lens = None
@@ -225,11 +252,11 @@ class Sampler(object):
         return Layouts(bbox_raw, bbox, overlap, alignment, order, cond.num, jit, mod, seeds)
 
 
-def generate_layouts(G, background, texts, labels, seeds, post_process=None, rng=None, strength=0.2, background_size=None):
+def generate_layouts(G, background, texts, labels, seeds, post_process=None, rng=None, strength=0.2, background_size=None, page_filter=None):
     """The one-call form.  post_process: None (no finishing), a dict of probabilities as generate_banners takes it (drawn by reference_plan from
     `rng`), or a list of (jitter, mode) per seed."""
     s = Sampler(G)
-    cond = s.encode(background, texts, labels, background_size=background_size)
+    cond = s.encode(background, texts, labels, background_size=background_size, page_filter=page_filter)
     seeds = list(seeds)
     if post_process is None:
         plan = [(False, NONE)] * len(seeds)
@@ -249,7 +276,9 @@ def build_parser():
     p = argparse.ArgumentParser(prog='python -m layoutdetr_amd.generate', description=__doc__.split('\n\n')[0])
     p.add_argument('--ckpt', '--network', dest='ckpt', required=True, help='snapshot written by training_loop.save_snapshot')
     p.add_argument('--bg', required=True, help='background image')
-    p.add_argument('--bg-preprocessing', default='none', choices=['none', '256', '128'], help='256 / 128: resize the page to that size instead of 1024')
+    p.add_argument('--bg-preprocessing', default='none', choices=BG_MODES,
+                   help="256 / 128: resize the page to that size instead of 1024; blur / edge: Gaussian blur (radius 3) / grey edge filter on the device, then "
+                        "resize to 1024; jpeg / rec: read <dir>_jpeg/<name>.jpg / <dir>_rec/<name> instead of the page; 3x_mask: the same as none (as in the reference)")
     p.add_argument('--strings', required=True, help="texts separated by '|'")
     p.add_argument('--string-labels', required=True, help="one label per text separated by '|': " + ', '.join(LABEL_LIST))
     p.add_argument('--seeds', type=parse_range, default=[0], help="e.g. '1,3-5'")
@@ -307,12 +336,13 @@ def draw_boxes(page, boxes, labels, path):
 def main(argv=None):
     import PIL.Image
     a = parse_args(argv)
+    path, page_filter, size = resolve_background(a.bg, a.bg_preprocessing)
     dev = torch.device('cuda')
     G = load_generator(a.ckpt, dev, a.vocab)
-    page = PIL.Image.open(a.bg).convert('RGB')
-    size = int(a.bg_preprocessing) if a.bg_preprocessing in ('256', '128') else 1024
+    page = PIL.Image.open(a.bg).convert('RGB')                     # what the boxes are drawn over: always the original page (generate.py:252)
+    seen = page if path == a.bg else PIL.Image.open(path).convert('RGB')
     s = Sampler(G)
-    cond = s.encode([torch.from_numpy(np.array(page))], [a.texts], [a.labels], background_size=size)
+    cond = s.encode([torch.from_numpy(np.array(seen))], [a.texts], [a.labels], background_size=size, page_filter=page_filter)
     K = len(a.seeds)
     res = s.sample(cond, seeds=a.seeds, jitter=[a.out_jittering_strength > 0.0] * K, modes=[a.mode] * K, strength=a.out_jittering_strength or 0.2)
     n = len(a.texts)

@@ -62,6 +62,7 @@ def calc_metric(metric, **kwargs): # See metric_utils_layout.MetricOptions for t
         total_time      = total_time,
         total_time_str  = metric_utils_layout.format_time(total_time),
         num_gpus        = opts.num_gpus,
+        background_filter = opts.background_filter,
     )
 
 #----------------------------------------------------------------------------

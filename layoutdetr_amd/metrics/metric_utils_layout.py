@@ -51,8 +51,13 @@ def format_time(seconds):
 
 class MetricOptions:
     def __init__(self, G=None, G_kwargs={}, dataset_kwargs={}, num_gpus=1, rank=0, device=None, progress=None, cache=True, run_dir=None,
-                 batch_size=8, cache_dir=None, data_loader_kwargs=None):
+                 batch_size=8, cache_dir=None, data_loader_kwargs=None, background_filter=None):
         assert 0 <= rank < num_gpus
+        if background_filter not in (None, 'blur', 'edge'):
+            raise ValueError(f"MetricOptions: background_filter must be None, 'blur' or 'edge' (got {background_filter!r})")
+        # every page the generator sees is filtered on the device before the resize (dataset_layoutganpp.filter_pages); the real-data side of a
+        # metric reads boxes only and does not depend on it, so the cache of real-data statistics keeps its key
+        self.background_filter = background_filter
         self.G = G
         self.G_kwargs = EasyDict(G_kwargs)
         self.dataset_kwargs = EasyDict(dataset_kwargs)
@@ -381,7 +386,7 @@ def _generator_batches(opts, walk, dataset):
     try:
         with torch.no_grad():
             for samples, labels, real in walk:
-                bt = assemble_batch(samples, labels, G, dataset.background_size_for_training, opts.device)
+                bt = assemble_batch(samples, labels, G, dataset.background_size_for_training, opts.device, page_filter=opts.background_filter)
                 B, N = bt['bbox_class'].shape
                 gen_z = torch.randn([B, N, G.z_dim], dtype=torch.float32, device=opts.device)
                 bbox_fake = G(z=gen_z, bbox_class=bt['bbox_class'], bbox_real=bt['bbox_real'], bbox_text=bt['bbox_text'], bbox_patch=bt['bbox_patch'],

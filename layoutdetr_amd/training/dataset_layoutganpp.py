@@ -57,16 +57,45 @@ def resample_coeffs(in_size, out_size, device):
     return out
 
 
-def background_to_tensor(pages_u8, background_size, return_u8=False, mean=RGB_MEAN, std=RGB_STD):
-    """Decoded pages, uint8 [n, H, W, 3] (or [H, W, 3]) in GPU memory -> float32 [n, 3, S, S]: what `_load_raw_data` returns under
-    'background', for the whole batch in two launches.  return_u8 additionally returns the resized uint8 pages [n, S, S, 3]."""
+PAGE_FILTER_TILE = 64                                   # csrc/page_filter.hip PF_TILE: one block per 64 x 64 output tile
+PAGE_FILTER_KINDS = {'blur': 1, 'edge': 2}              # include/ldetr_hip.h LDETR_PAGE_FILTER_*
+
+
+def filter_pages(pages_u8, kind, radius=3.0):
+    """The page filters of the reference's generate.py --bg-preprocessing on decoded pages, uint8 [n, H, W, 3] (or [H, W, 3]) in GPU memory ->
+    a new tensor of the same shape, one launch for all pages (csrc/page_filter.hip), bit-identical to Pillow:
+    'blur' = ImageFilter.GaussianBlur(radius), 0 < radius <= 5 (generate.py:268); 'edge' = convert('L').filter(FIND_EDGES).convert('RGB') (:281)."""
     core.require_gpu(pages_u8)
+    if kind not in PAGE_FILTER_KINDS:
+        raise ValueError(f'filter_pages: unknown kind {kind!r}: one of {sorted(PAGE_FILTER_KINDS)}')
+    if pages_u8.dtype != torch.uint8 or pages_u8.ndim not in (3, 4) or pages_u8.shape[-1] != 3 or 0 in pages_u8.shape[-3:]:
+        raise ValueError(f'filter_pages: expected uint8 [n, H, W, 3] or [H, W, 3] (got {pages_u8.dtype} {tuple(pages_u8.shape)})')
+    radius = float(radius)
+    if kind == 'blur' and not 0.0 < radius <= 5.0:
+        raise ValueError(f'filter_pages: blur radius must be in (0, 5] (got {radius})')
+    src = pages_u8.contiguous()
+    if src.data_ptr() % 4:                              # a view that starts in the middle of a buffer: the kernel loads 4 bytes at a time
+        src = src.clone()
+    out = torch.empty_like(src)
+    n = src.shape[0] if src.ndim == 4 else 1
+    H, W = src.shape[-3], src.shape[-2]
+    core.check(core.lib().ldetr_page_filter_u8(core.ptr(src), core.ptr(out), n, H, W, PAGE_FILTER_KINDS[kind], radius, core.stream()), 'page_filter_u8')
+    return out
+
+
+def background_to_tensor(pages_u8, background_size, return_u8=False, mean=RGB_MEAN, std=RGB_STD, page_filter=None):
+    """Decoded pages, uint8 [n, H, W, 3] (or [H, W, 3]) in GPU memory -> float32 [n, 3, S, S]: what `_load_raw_data` returns under
+    'background', for the whole batch in two launches.  return_u8 additionally returns the resized uint8 pages [n, S, S, 3].
+    page_filter ('blur' / 'edge'; None: nothing changes) runs `filter_pages` on the pages before the resize, as generate.py:267-269, 280-282."""
+    core.require_gpu(pages_u8)
+    if page_filter is not None and page_filter not in PAGE_FILTER_KINDS:
+        raise ValueError(f'background_to_tensor: page_filter must be None or one of {sorted(PAGE_FILTER_KINDS)} (got {page_filter!r})')
     single = pages_u8.ndim == 3
     if single:
         pages_u8 = pages_u8[None]
     if pages_u8.dtype != torch.uint8 or pages_u8.ndim != 4 or pages_u8.shape[-1] != 3:
         raise ValueError('background_to_tensor: expected uint8 [n, H, W, 3] (the reference asserts 3 channels, dataset_layoutganpp.py:334)')
-    pages_u8 = pages_u8.contiguous()
+    pages_u8 = pages_u8.contiguous() if page_filter is None else filter_pages(pages_u8, page_filter)
     n, H, W, _ = pages_u8.shape
     S = int(background_size)
     dev = pages_u8.device
@@ -360,20 +389,26 @@ class LayoutDataset(Dataset):
         return out, torch.from_numpy(np.stack(labels, 0))
 
 
-def batch_backgrounds_to_device(background, background_size, device):
+def batch_backgrounds_to_device(background, background_size, device, page_filter=None):
     """'background' of a collated batch -> float32 [B, 3, S, S] on `device`.  uint8 pages (mode='device': one [B, H, W, 3] tensor, or a
     list when page sizes differ) are uploaded as bytes and resized + normalised by `background_to_tensor`, one call per distinct page
-    size; float input (mode='reference' / other datasets) is what the reference already hands over (training_loop.py:264)."""
+    size; float input (mode='reference' / other datasets) is what the reference already hands over (training_loop.py:264).
+    page_filter ('blur' / 'edge') filters the uint8 pages before the resize; float backgrounds are already resized, so a filter on them raises."""
+    if page_filter is not None and page_filter not in PAGE_FILTER_KINDS:
+        raise ValueError(f'batch_backgrounds_to_device: page_filter must be None or one of {sorted(PAGE_FILTER_KINDS)} (got {page_filter!r})')
     if torch.is_tensor(background):
         if background.dtype != torch.uint8:
+            if page_filter is not None:
+                raise ValueError('batch_backgrounds_to_device: page_filter needs the decoded uint8 pages (dataset mode=\'device\'), not float backgrounds')
             return background.to(device).float()
-        return background_to_tensor(background.to(device, non_blocking=True), background_size)
+        return background_to_tensor(background.to(device, non_blocking=True), background_size, page_filter=page_filter)
     groups = {}
     for i, p in enumerate(background):
         groups.setdefault(tuple(p.shape), []).append(i)
     out = torch.empty((len(background), 3, background_size, background_size), dtype=torch.float32, device=device)
     for idx in groups.values():
-        out[torch.tensor(idx, device=device)] = background_to_tensor(torch.stack([background[i] for i in idx]).to(device, non_blocking=True), background_size)
+        out[torch.tensor(idx, device=device)] = background_to_tensor(torch.stack([background[i] for i in idx]).to(device, non_blocking=True), background_size,
+                                                                         page_filter=page_filter)
     return out
 
 

@@ -857,10 +857,11 @@ class InfiniteSampler(torch.utils.data.Sampler):
             idx += 1
 
 
-def assemble_batch(samples, real_c, G, background_size, device):
+def assemble_batch(samples, real_c, G, background_size, device, page_filter=None):
     """One collated DataLoader batch -> the keyword tensors G / D / the loss take, on `device` (reference training_loop.py:246-264): device collate,
     strings -> tokens ONCE (the reference re-tokenises inside each forward), the 0-stride patch placeholder, the page background resized and
-    normalised on the GPU.  Shared by the training loop and the metric passes (metrics/metric_utils_layout.py)."""
+    normalised on the GPU.  Shared by the training loop and the metric passes (metrics/metric_utils_layout.py; `page_filter` is theirs: 'blur' /
+    'edge' on the uint8 pages before the resize, MetricOptions.background_filter)."""
     from .dataset_layoutganpp import batch_backgrounds_to_device, patch_placeholder_to_device
     texts = list(map(list, zip(*samples['texts']))) if isinstance(samples.get('texts'), (list, tuple)) else samples['texts']   # :246
     if isinstance(texts, list) and hasattr(G, 'tokenizer'):
@@ -868,7 +869,7 @@ def assemble_batch(samples, real_c, G, background_size, device):
         texts = _coerce_text(G, texts, device)
     return dict(bbox_real=samples['bboxes'].to(device).float(), bbox_class=samples['labels'].to(device).long(), bbox_text=texts,
                 bbox_patch=patch_placeholder_to_device(samples['patches'], device), padding_mask=~samples['mask'].to(device).bool(),
-                background=batch_backgrounds_to_device(samples['background'], background_size, device),
+                background=batch_backgrounds_to_device(samples['background'], background_size, device, page_filter=page_filter),
                 real_c=real_c.to(device))
 
 
