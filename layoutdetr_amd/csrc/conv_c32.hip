@@ -23,8 +23,6 @@
 
 namespace ldetr {
 
-bool engine_split_enabled();      // gemm_conv.hip: ldetr_set_split_bf16 / LDETR_DEBUG="SPLIT_BF16=0"
-
 struct ConvC32Params {
     const float* x; float* y; const float* w;                  // x, y: [N, H, W, 32] packed; w: [32 out][3][3][32 in] (OHWI)
     const float* k_scale; long k_scale_ld;                      // per sample, per input channel of THIS contraction (style / demod), or null

@@ -8,12 +8,15 @@
 // matrices, or NHWC gathers (im2col is never materialised).  All activations are NHWC
 // (channels_last) so the reduction index (tap, channel) is contiguous along channels.
 //
-// Arithmetic: v_mfma_f32_32x32x2_f32 — exact fp32 products and accumulation (the reference step is
-// fp32 end-to-end with TF32 disabled, training/training_loop.py:104-105).  Peak 157 TFLOP/s.
-// Tiling: 256 threads = 4 waves (2x2); block tile 128x128 (BK 16) or 64x64 (BK 32); LDS tiles are
-// k-major ([k][row], row stride R+2 -> conflict-free MFMA operand reads and transposing writes),
-// double-buffered with register staging (global loads for tile t+1 are in flight during the
-// MFMAs of tile t; one barrier per k-tile).
+// Arithmetic, on either matrix pipe with fp32 results: v_mfma_f32_32x32x2_f32 -- exact fp32 products and accumulation (the reference step is
+// fp32 end-to-end with TF32 disabled, training/training_loop.py:104-105), peak 157 TFLOP/s -- or the bf16 MFMAs over the exact three-way split
+// of both operands (the SPLIT instantiation, see gemm_f32_kernel).
+// gemm_f32_kernel, the tiled kernel: block tiles 64x64, 128x64, 128x128 and (narrow outputs) 256x32, BK 32, 4 or 8 waves.  On the f32 pipe the
+// LDS tiles are k-major ([k][row], row stride R+2 -> conflict-free MFMA operand reads and transposing writes), double-buffered with register
+// staging (global loads for tile t+1 are in flight during the MFMAs of tile t; one barrier per k-tile).
+// gemm_small_kernel / gemm_small_pair_kernel, the small-tile kernels: 32x32 tiles streamed through registers for the latency-bound problems (few
+// tiles), one problem or two per launch, with an in-kernel split-K of their own.
+// The host part closes the file: the workspace rings, the launch policy (launch_small, launch_gemm) and the C entry points.
 #include <cstdlib>
 #include <type_traits>
 #include <atomic>
@@ -21,15 +24,8 @@
 #include "../../include/ldetr_hip.h"
 
 namespace ldetr {
-int try_launch_stem_conv(const float* x, const ldetr_tensor4* xt, const float* w, int Cout, int KH, int KW, int stride, int pad,
-                         float* y, long ldy, int OH, int OW, const float* in_scale, const ldetr_epilogue* ep, hipStream_t st);
-int try_launch_conv_c32(const float* x, const ldetr_tensor4* xt, const float* w, int Cout, int KH, int KW, int stride, int pad,
-                        float* y, long ldy, int OH, int OW, const float* k_scale, long k_scale_ld, const ldetr_epilogue* ep,
-                        int transposed, hipStream_t st);
 static thread_local int64_t t_launches_f32 = 0, t_launches_split = 0;   // ldetr_engine_launch_counts: contraction kernels issued by this thread, by matrix pipe
-void note_engine_launch(bool bf16_split_pipe) { (bf16_split_pipe ? t_launches_split : t_launches_f32)++; }   // contraction kernels of other translation units (p3_engine.hip)
-int try_launch_wgrad_smallc(const float* x, const ldetr_tensor4* xt, const float* dy, const ldetr_tensor4* dyt, float* dw, int KH, int KW, int stride, int pad,
-                            const float* x_scale, int64_t x_scale_ld, const float* dy_scale, int64_t dy_scale_ld, hipStream_t st);
+void count_engine_launch(bool bf16_split_pipe) { (bf16_split_pipe ? t_launches_split : t_launches_f32)++; }   // contraction kernels of other translation units (p3_engine.hip)
 
 enum {
     OP_KC_DENSE = 0,  // (row r, k): src[r*ld + k]
@@ -1384,6 +1380,32 @@ static Workspace& workspace_for_current_device() {
     return g_workspace[dev];
 }
 
+// The one place slices are handed out: `tiles` arrival counters (may be 0) and `bytes` of partial tiles (rounded up to 256), each from its
+// ring's cursor, which wraps to the start when the request does not fit behind it.  false when no workspace is registered or the request
+// exceeds a whole ring.
+static bool ring_alloc(long tiles, size_t bytes, int** counters, float** partials) {
+    Workspace& w = workspace_for_current_device();
+    const size_t need = (bytes + 255) & ~(size_t)255;
+    const size_t pbytes = w.bytes > WS_COUNTERS * sizeof(int) ? w.bytes - WS_COUNTERS * sizeof(int) : 0;
+    if (!w.ptr || need > pbytes || tiles > WS_COUNTERS) return false;
+    if (w.counter_cursor + tiles > (size_t)WS_COUNTERS) w.counter_cursor = 0;
+    if (w.partial_cursor + need > pbytes) w.partial_cursor = 0;
+    *counters = reinterpret_cast<int*>(w.ptr) + w.counter_cursor;
+    *partials = reinterpret_cast<float*>(reinterpret_cast<char*>(w.ptr) + WS_COUNTERS * sizeof(int) + w.partial_cursor);
+    w.counter_cursor += tiles; w.partial_cursor += need;
+    return true;
+}
+
+// Split-K scratch for the other contraction kernels of the library (p3_engine.hip) and transient scratch for its other kernels (partial sums
+// of the row reductions), from the same rings: a slice is valid for the launches the caller enqueues next on its stream.  false / nullptr when
+// no workspace is registered or the request does not fit.
+bool splitk_ws_alloc(long tiles, size_t partial_bytes, float** ws, int** counters) { return ring_alloc(tiles, partial_bytes, counters, ws); }
+
+float* scratch_alloc(size_t bytes) {
+    int* counters; float* r;
+    return ring_alloc(0, bytes, &counters, &r) ? r : nullptr;
+}
+
 // Split-K plan of a small-tile problem: few tiles + a long reduction (the decoders' 2048-wide FFN on 144 rows) would have 40 blocks
 // walk K one after the other; split K over up to 8 blocks per tile (>= 256 of K each) and reduce through the workspace in-kernel.
 static int plan_small_split(GemmParams& p, long blocks) {
@@ -1391,18 +1413,7 @@ static int plan_small_split(GemmParams& p, long blocks) {
     if (blocks <= 128 && p.K >= 1024) {
         sk = p.K / 256; if (sk > 8) sk = 8;
         while (sk > 1 && blocks * sk > 640) sk--;
-        if (sk > 1) {
-            Workspace& w = workspace_for_current_device();
-            const size_t need = ((size_t)blocks * sk * 1024 * sizeof(float) + 255) & ~(size_t)255;
-            const size_t pbytes = w.bytes > WS_COUNTERS * sizeof(int) ? w.bytes - WS_COUNTERS * sizeof(int) : 0;
-            if (w.ptr && need <= pbytes) {
-                if (w.counter_cursor + blocks > (size_t)WS_COUNTERS) w.counter_cursor = 0;
-                if (w.partial_cursor + need > pbytes) w.partial_cursor = 0;
-                p.ws_count = reinterpret_cast<int*>(w.ptr) + w.counter_cursor;
-                p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(w.ptr) + WS_COUNTERS * sizeof(int) + w.partial_cursor);
-                w.counter_cursor += blocks; w.partial_cursor += need;
-            } else sk = 1;
-        }
+        if (sk > 1 && !ring_alloc(blocks, (size_t)blocks * sk * 1024 * sizeof(float), &p.ws_count, &p.ws)) sk = 1;
     }
     return sk;
 }
@@ -1414,25 +1425,53 @@ static bool small_fast_ok(const GemmParams& p, int ta, int tb) {
            ((((uintptr_t)p.A.p) | ((uintptr_t)p.B.p)) & 15) == 0;
 }
 
+// 8 waves per block: few blocks, each with a long reduction of its own
+static bool small_wants8(long blocks, int sk, int K) { return blocks * sk <= 256 && (K + sk - 1) / sk >= 512; }
+
+// The small-tile kernels by operand modes: (TA, TB) -> gemm_small_kernel, (TA0, TB0, TA1, TB1) -> gemm_small_pair_kernel.
+template <int NW, bool FAST, int TA, int TB>
+static auto small_kernel() { return gemm_small_kernel<TA, TB, NW, FAST>; }
+template <int NW, bool FAST, int TA0, int TB0, int TA1, int TB1>
+static auto small_kernel() { return gemm_small_pair_kernel<TA0, TB0, TA1, TB1, NW, FAST>; }
+
+// One launch ladder for both: the FAST (scalar-addressed loads) x 8-wave instantiation of the kernel MODES names.
+template <int... MODES, typename... Args>
+static void launch_small_kernel(bool fast, bool w8, dim3 grid, hipStream_t st, const Args&... args) {
+    if (fast) {
+        if (w8) hipLaunchKernelGGL((small_kernel<8, true, MODES...>()), grid, 512, 0, st, args...);
+        else hipLaunchKernelGGL((small_kernel<4, true, MODES...>()), grid, 256, 0, st, args...);
+    } else {
+        if (w8) hipLaunchKernelGGL((small_kernel<8, false, MODES...>()), grid, 512, 0, st, args...);
+        else hipLaunchKernelGGL((small_kernel<4, false, MODES...>()), grid, 256, 0, st, args...);
+    }
+    t_launches_f32++;
+}
+
 template <int TA, int TB>
 static int launch_small(GemmParams& p, hipStream_t st) {
     dim3 grid(cdiv(p.N, 32), cdiv(p.M, 32), 1);
     const long blocks = (long)grid.x * grid.y;
     const int sk = plan_small_split(p, blocks);
     grid.z = sk;
-    const int kblock = (p.K + sk - 1) / sk;
     const bool fast = small_fast_ok(p, TA, TB);
-    const bool w8 = blocks * sk <= 256 && kblock >= 512;
-    if (fast) {
-        if (w8) hipLaunchKernelGGL((gemm_small_kernel<TA, TB, 8, true>), grid, 512, 0, st, p);
-        else hipLaunchKernelGGL((gemm_small_kernel<TA, TB, 4, true>), grid, 256, 0, st, p);
-    } else {
-        if (w8) hipLaunchKernelGGL((gemm_small_kernel<TA, TB, 8>), grid, 512, 0, st, p);
-        else hipLaunchKernelGGL((gemm_small_kernel<TA, TB, 4>), grid, 256, 0, st, p);
-    }
-    t_launches_f32++;
+    const bool w8 = small_wants8(blocks, sk, p.K);
+    launch_small_kernel<TA, TB>(fast, w8, grid, st, p);
     note_engine_launch(2, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, sk, blocks * sk, TA * 2 + TB);
     return check_launch("gemm_small");
+}
+
+// Two small-tile problems as ONE launch (gemm_small_pair_kernel): (TA0, 1) + (1, 1); each problem may carry its own in-kernel split-K.
+template <int TA0>
+static int launch_small_pair(GemmParams& p0, GemmParams& p1, hipStream_t st) {
+    const int gx0 = cdiv(p0.N, 32), nt0 = gx0 * cdiv(p0.M, 32), gx1 = cdiv(p1.N, 32), nt1 = gx1 * cdiv(p1.M, 32);
+    const int sk0 = plan_small_split(p0, nt0), sk1 = plan_small_split(p1, nt1);
+    // one block size for both: 8 waves only when both problems would take them on their own
+    const bool w8 = small_wants8(nt0, sk0, p0.K) && small_wants8(nt1, sk1, p1.K);
+    const bool fast = small_fast_ok(p0, TA0, 1) && small_fast_ok(p1, 1, 1);
+    const dim3 grid((unsigned)(nt0 * sk0 + nt1 * sk1));
+    launch_small_kernel<TA0, 1, 1, 1>(fast, w8, grid, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
+    note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, sk0 * 256 + sk1, (long)grid.x, (TA0 * 2 + 1) * 4 + 3);
+    return check_launch("gemm_small_pair");
 }
 
 // Second phase of a split-K contraction: C holds sum_k (already scaled by alpha); apply the rest of the epilogue in place.
@@ -1456,8 +1495,6 @@ static bool epilogue_is_linear(const GemmEpilogue& ep) {
            ep.out_scale == 1.f;
 }
 
-
-static void init_operand(Operand& o) { memset(&o, 0, sizeof(o)); o.KW = 1; o.KH = 1; o.stride = 1; o.C = 1; o.Cr = 1; }
 
 // Launch policy.  Tile 128x128 (BK 16) when it alone fills the chip; otherwise 64x64 (BK 32), and when even those
 // tiles leave most of the 256 CUs idle the reduction is split across grid.z (fp32 atomics into a zeroed C) with
@@ -1485,37 +1522,10 @@ static void init_operand(Operand& o) { memset(&o, 0, sizeof(o)); o.KW = 1; o.KH 
 // Dense GEMMs with fewer 64x64 tiles than this (and at most this much work) take the register-streaming 32x32 kernel.
 static const long SMALL_GEMM_TILES = 256;   // 64x64-tile count below which the small-tile kernels run
 constexpr long SMALL_GEMM_MNK = 1l << 30;
+static bool small_class(long M, long N, long K) { return (long)cdiv(M, 64) * cdiv(N, 64) < SMALL_GEMM_TILES && M * N * K <= SMALL_GEMM_MNK; }
 #ifndef WGRAD_MIN_K
 #define WGRAD_MIN_K 512
 #endif
-
-// Transient scratch for other kernels of the library (partial sums of the row reductions): a slice of the same ring, valid for
-// the launches the caller enqueues next on its stream.  nullptr when no workspace is registered or the request does not fit.
-// Split-K scratch for the other contraction kernels of the library (p3_engine.hip): `tiles` arrival counters + `partial_bytes` of partial tiles
-// from the same rings; false if no workspace is registered or it is too small.
-bool splitk_ws_alloc(long tiles, size_t partial_bytes, float** ws, int** counters) {
-    Workspace& w = workspace_for_current_device();
-    const size_t need = (partial_bytes + 255) & ~(size_t)255;
-    const size_t pbytes = w.bytes > WS_COUNTERS * sizeof(int) ? w.bytes - WS_COUNTERS * sizeof(int) : 0;
-    if (!w.ptr || need > pbytes || tiles > WS_COUNTERS) return false;
-    if (w.counter_cursor + tiles > (size_t)WS_COUNTERS) w.counter_cursor = 0;
-    if (w.partial_cursor + need > pbytes) w.partial_cursor = 0;
-    *counters = reinterpret_cast<int*>(w.ptr) + w.counter_cursor;
-    *ws = reinterpret_cast<float*>(reinterpret_cast<char*>(w.ptr) + WS_COUNTERS * sizeof(int) + w.partial_cursor);
-    w.counter_cursor += tiles; w.partial_cursor += need;
-    return true;
-}
-
-float* scratch_alloc(size_t bytes) {
-    Workspace& w = workspace_for_current_device();
-    const size_t pbytes = w.bytes > WS_COUNTERS * sizeof(int) ? w.bytes - WS_COUNTERS * sizeof(int) : 0;
-    bytes = (bytes + 255) & ~(size_t)255;
-    if (!w.ptr || bytes > pbytes) return nullptr;
-    if (w.partial_cursor + bytes > pbytes) w.partial_cursor = 0;
-    float* r = reinterpret_cast<float*>(reinterpret_cast<char*>(w.ptr) + WS_COUNTERS * sizeof(int) + w.partial_cursor);
-    w.partial_cursor += bytes;
-    return r;
-}
 
 // Zero-fill of a pitched fp32 matrix for the atomic split-K path.  A kernel rather than hipMemset2DAsync: memset nodes captured into
 // a hipGraph were observed to replay out of order with their neighbouring kernel nodes on ROCm 7.2 (garbage gradients on replay).
@@ -1538,15 +1548,31 @@ static int zero_fill(float* dst, long pitch, long width, long rows, hipStream_t 
 static long long* g_trace_buffer = nullptr;   // ldetr_debug_trace_tiles
 static std::atomic<int> g_split_bf16_override{-1};   // ldetr_set_split_bf16: -1 = environment / default, else the tile mask (process-wide; atomic: tests toggle it while other host threads may launch)
 
+// Tiles that may take the bf16 split path: ldetr_set_split_bf16's mask if one is set, else LDETR_DEBUG="SPLIT_BF16=mask".
+static int split_bf16_tiles() {
+    static const int env = (int)knob("SPLIT_BF16", 15);   // bit 0: 128x128, bit 1: 128x64, bit 2: 256x32, bit 3: 64x64
+    const int ovr = g_split_bf16_override.load(std::memory_order_relaxed);
+    return ovr >= 0 ? ovr : env;
+}
+// (conv_c32.hip follows the same switch: value_f32_mfma_only of the bench line and the f32-pipe halves of the parity tests cover it too)
+bool engine_split_enabled() { return split_bf16_tiles() != 0; }
+
+// The operand views that have a scalar-addressed (FAST) instantiation of the tiled kernel; a pair is capable when either side is.
+template <int AMODE>
+constexpr bool fast_cap_a = (AMODE == OP_KC_CONV || AMODE == OP_KC_CONVT || AMODE == OP_KC_DENSE || AMODE == OP_RC_DENSE || AMODE == OP_RC_PIX);
+template <int BMODE>
+constexpr bool fast_cap_b = (BMODE == OP_KC_DENSE || BMODE == OP_RC_WT || BMODE == OP_RC_DENSE || BMODE == OP_RC_PIX || BMODE == OP_KC_WTAP);
+template <int AMODE, int BMODE>
+constexpr bool fast_cap = fast_cap_a<AMODE> || fast_cap_b<BMODE>;
+
 // Host-side conditions of the kernel's scalar-addressed loads (FAST instantiation): every operand whose view supports them must
 // qualify, otherwise the generic instantiation runs.  BKT is 32 for every tile shape.
 template <int AMODE, int BMODE>
 static bool fast_operands_ok(const GemmParams& p, int Mmax) {
     static const int fast_loads = (int)knob("FAST_LOADS", 63);   // 1 conv, 2 dense B, 4 transposed conv, 8 dense A, 16 row-contiguous dense, 32 pixel-major (weight gradient input)
     constexpr int BKT = 32;
-    constexpr bool a_cap = (AMODE == OP_KC_CONV || AMODE == OP_KC_CONVT || AMODE == OP_KC_DENSE || AMODE == OP_RC_DENSE || AMODE == OP_RC_PIX);
-    constexpr bool b_cap = (BMODE == OP_KC_DENSE || BMODE == OP_RC_WT || BMODE == OP_RC_DENSE || BMODE == OP_RC_PIX || BMODE == OP_KC_WTAP);
-    if (!a_cap && !b_cap) return false;
+    constexpr bool a_cap = fast_cap_a<AMODE>;
+    if (!fast_cap<AMODE, BMODE>) return false;
     const long lim = 0x7fffffffL;
     auto taps_ok = [&](int C, int KH, int KW) {   // a k-tile never straddles a tap (C == k-tile measured slower: 483 vs 420 us on the 32-channel 256^2 layer)
         return C > 0 && (C % BKT) == 0 && C >= (p.narrow ? BKT : 2 * BKT) && (long)KH * KW <= 32 && p.samp_pix == 0;
@@ -1625,8 +1651,7 @@ static int launch_tile_impl(GemmParams& p, dim3 grid, hipStream_t st) {
 
 template <int BM, int BN, int BKT, int AMODE, int BMODE, int NWV = 4>
 static int launch_tile(GemmParams& p, dim3 grid, int Mmax, hipStream_t st) {
-    constexpr bool cap = (AMODE == OP_KC_CONV || AMODE == OP_KC_CONVT || AMODE == OP_KC_DENSE || AMODE == OP_RC_DENSE || AMODE == OP_RC_PIX || BMODE == OP_KC_DENSE || BMODE == OP_RC_WT || BMODE == OP_RC_DENSE || BMODE == OP_RC_PIX || BMODE == OP_KC_WTAP);
-    if constexpr (cap) {
+    if constexpr (fast_cap<AMODE, BMODE>) {
         if (fast_operands_ok<AMODE, BMODE>(p, Mmax)) return launch_tile_impl<BM, BN, BKT, AMODE, BMODE, NWV, true>(p, grid, st);
     }
     return launch_tile_impl<BM, BN, BKT, AMODE, BMODE, NWV, false>(p, grid, st);
@@ -1678,20 +1703,9 @@ static int launch_gemm(GemmParams& p, int Mmax, long out_rows, int zbase, bool a
     bool fixup = false;
     if (split && !(caller_zeroed && epilogue_is_linear(p.ep)) && !(p.ep.accumulate && epilogue_is_linear(p.ep))) {
         // in-kernel fix-up when the caller registered a workspace that can hold this launch's partial tiles
-        Workspace& w = workspace_for_current_device();
         const int bm = (use128 || use12864) ? 128 : 64, bn = use128 ? 128 : 64;
         const long tiles = (long)cdiv(p.N, bn) * cdiv(Mmax, bm) * zbase;
-        const size_t need = ((size_t)tiles * p.splitk * bm * bn * sizeof(float) + 255) & ~(size_t)255;
-        const size_t pbytes = w.bytes > WS_COUNTERS * sizeof(int) ? w.bytes - WS_COUNTERS * sizeof(int) : 0;
-        if (w.ptr && tiles <= WS_COUNTERS && need <= pbytes) {
-            if (w.counter_cursor + tiles > (size_t)WS_COUNTERS) w.counter_cursor = 0;
-            if (w.partial_cursor + need > pbytes) w.partial_cursor = 0;
-            p.ws_count = reinterpret_cast<int*>(w.ptr) + w.counter_cursor;
-            p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(w.ptr) + WS_COUNTERS * sizeof(int) + w.partial_cursor);
-            w.counter_cursor += tiles;
-            w.partial_cursor += need;
-            fixup = true;
-        }
+        fixup = ring_alloc(tiles, (size_t)tiles * p.splitk * bm * bn * sizeof(float), &p.ws_count, &p.ws);
     }
     if (split && !fixup) {
         if (!p.ep.accumulate && !caller_zeroed) {
@@ -1705,34 +1719,30 @@ static int launch_gemm(GemmParams& p, int Mmax, long out_rows, int zbase, bool a
                    ok4(e.residual, e.ldr) && ok4(e.samp_scale, e.samp_ld) && ok4(e.mask_mode ? e.mask_src : nullptr, e.ldm) && !p.srow && !p.scol && !e.row_scale && LDETR_EPILOGUE_VEC;
     }
     dim3 grid(cdiv(p.N, use128 ? 128 : 64), cdiv(Mmax, (use128 || use12864) ? 128 : 64), zbase * (split ? p.splitk : 1));
-    int rc;
     // bf16 split path (see gemm_f32_kernel): the 128-row tiles and the narrow tile, scalar-addressed operands only; four waves per
     // block so that every wave owns >= two 32x32 accumulators (LDS operand bytes per MFMA halve with each doubling of the wave tile)
-    constexpr bool split_cap = (AMODE == OP_KC_CONV || AMODE == OP_KC_CONVT || AMODE == OP_KC_DENSE || AMODE == OP_RC_DENSE || AMODE == OP_RC_PIX || BMODE == OP_KC_DENSE || BMODE == OP_RC_WT || BMODE == OP_RC_DENSE || BMODE == OP_RC_PIX || BMODE == OP_KC_WTAP);
-    static const int split_tiles_env = (int)knob("SPLIT_BF16", 15);   // bit 0: 128x128, bit 1: 128x64, bit 2: 256x32, bit 3: 64x64
     constexpr int split_min_kk = 128;
-    const int split_ovr = g_split_bf16_override.load(std::memory_order_relaxed);
-    const int split_tiles = split_ovr >= 0 ? split_ovr : split_tiles_env;
-    const int split_on = split_tiles;
+    const int split_tiles = split_bf16_tiles();
     bool sp = false;
-    if constexpr (split_cap) sp = split_on && (p.K / (split ? p.splitk : 1)) >= split_min_kk && fast_operands_ok<AMODE, BMODE>(p, Mmax);
+    if constexpr (fast_cap<AMODE, BMODE>) sp = split_tiles && (p.K / (split ? p.splitk : 1)) >= split_min_kk && fast_operands_ok<AMODE, BMODE>(p, Mmax);
     if constexpr (narrow_cap) {
         if (use_narrow) {
-            if constexpr (split_cap) { if (sp && (split_on & 4)) return launch_tile_impl<256, 32, 32, AMODE, BMODE, 4, true, true>(p, dim3(1, cdiv(Mmax, 256), zbase), st); }
+            if constexpr (fast_cap<AMODE, BMODE>) { if (sp && (split_tiles & 4)) return launch_tile_impl<256, 32, 32, AMODE, BMODE, 4, true, true>(p, dim3(1, cdiv(Mmax, 256), zbase), st); }
             return launch_tile<256, 32, 32, AMODE, BMODE, 4>(p, dim3(1, cdiv(Mmax, 256), zbase), Mmax, st);
         }
     }
-    bool sp_done = false;
-    rc = 0;
-    if constexpr (split_cap) {
-        if (sp && use128 && (split_on & 1)) { rc = launch_tile_impl<128, 128, 32, AMODE, BMODE, 4, true, true>(p, grid, st); sp_done = true; }
-        else if (sp && use12864 && (split_on & 2)) { rc = launch_tile_impl<128, 64, 32, AMODE, BMODE, 4, true, true>(p, grid, st); sp_done = true; }
-        else if (sp && !use128 && !use12864 && (split_on & 8)) { rc = launch_tile_impl<64, 64, 32, AMODE, BMODE, 4, true, true>(p, grid, st); sp_done = true; }
+    int rc = LDETR_OK;
+    if constexpr (fast_cap<AMODE, BMODE>) {
+        if (sp && use128 && (split_tiles & 1)) rc = launch_tile_impl<128, 128, 32, AMODE, BMODE, 4, true, true>(p, grid, st);
+        else if (sp && use12864 && (split_tiles & 2)) rc = launch_tile_impl<128, 64, 32, AMODE, BMODE, 4, true, true>(p, grid, st);
+        else if (sp && !use128 && !use12864 && (split_tiles & 8)) rc = launch_tile_impl<64, 64, 32, AMODE, BMODE, 4, true, true>(p, grid, st);
+        else sp = false;   // this tile shape stays on the f32 pipe
     }
-    if (sp_done) {}
-    else if (use128) rc = launch_tile<128, 128, T128_BK, AMODE, BMODE, T128_WAVES>(p, grid, Mmax, st);
-    else if (use12864) rc = launch_tile<128, 64, T12864_BK, AMODE, BMODE, T12864_WAVES>(p, grid, Mmax, st);
-    else rc = launch_tile<64, 64, 32, AMODE, BMODE>(p, grid, Mmax, st);
+    if (!sp) {
+        if (use128) rc = launch_tile<128, 128, T128_BK, AMODE, BMODE, T128_WAVES>(p, grid, Mmax, st);
+        else if (use12864) rc = launch_tile<128, 64, T12864_BK, AMODE, BMODE, T12864_WAVES>(p, grid, Mmax, st);
+        else rc = launch_tile<64, 64, 32, AMODE, BMODE>(p, grid, Mmax, st);
+    }
     if (rc) return rc;
     if (split && !fixup && !epilogue_is_linear(full)) {
         EpiParams q;
@@ -1749,13 +1759,6 @@ static int launch_gemm(GemmParams& p, int Mmax, long out_rows, int zbase, bool a
 // Weight gradients reduce over pixels (K = N*OH*OW, up to 2^20) into a small [Cout, taps, Cin] output: pick the tile
 // first (128-wide tiles when the channel counts allow them: two accumulator chains per wave, fewer LDS reads per MFMA),
 // then split K until that tile's grid fills the chip.  Mirrors the tile thresholds of launch_gemm.
-// (conv_c32.hip follows the same switch: value_f32_mfma_only of the bench line and the f32-pipe halves of the parity tests cover it too)
-bool engine_split_enabled() {
-    static const int split_tiles_env = (int)knob("SPLIT_BF16", 15);
-    const int ovr = g_split_bf16_override.load(std::memory_order_relaxed);
-    return (ovr >= 0 ? ovr : split_tiles_env) != 0;
-}
-
 static int wgrad_auto_split(int M, int N, int K, int zbase) {
     // few pixels (small per-GPU batches): shorter slices keep the chip busy; the floor of a weight-gradient launch is its serial k-loop
     // (measured: 128-pixel slices help at 2 samples per GPU, 25.3 -> 24.8 ms per step, and cost 4 % at 16 per GPU: keyed on the launch's work)
@@ -1804,12 +1807,36 @@ static void fill_epilogue(GemmEpilogue& ep, const ldetr_epilogue* e) {
     ep.a_rowsum = e->a_rowsum;
 }
 
+static void init_operand(Operand& o) { memset(&o, 0, sizeof(o)); o.KW = 1; o.KH = 1; o.stride = 1; o.C = 1; o.Cr = 1; }
+
+// Every entry point starts from this: a zeroed problem whose operands are plain dense views.
+static GemmParams new_params() {
+    GemmParams p; memset(&p, 0, sizeof(p));
+    init_operand(p.A); init_operand(p.B);
+    return p;
+}
+
+static void set_conv_src(Operand& o, const float* x, const ldetr_tensor4* t) {
+    o.p = x; o.SH = t->H; o.SW = t->W; o.sn = t->sn; o.sh = t->sh; o.sw = t->sw; o.sc = t->sc;
+}
+
+// An NHWC gather operand: source tensor, destination pixel grid and window, optional per-sample per-channel scale.  vec = float4 loads are legal:
+// 16-byte aligned base and scale, pixel / row / sample strides and the scale's pitch multiples of 4 (call sites with further conditions AND
+// them on afterwards).
+static void set_conv_operand(Operand& o, const float* x, const ldetr_tensor4* t, const float* scale, long scale_ld, int DH, int DW,
+                             int stride, int pad, int KH, int KW) {
+    set_conv_src(o, x, t);
+    o.DH = DH; o.DW = DW; o.stride = stride; o.pad = pad; o.KH = KH; o.KW = KW;
+    o.scale = scale; o.scale_ld = scale_ld;
+    o.vec = al16(x) && (t->sn % 4 == 0) && (t->sh % 4 == 0) && (t->sw % 4 == 0) && (!scale || (al16(scale) && scale_ld % 4 == 0));
+}
+
+static bool packed_nhwc(const ldetr_tensor4* t) { return t->sw == t->C && t->sh == (long)t->W * t->C && t->sn == (long)t->H * t->W * t->C; }
+
 }  // namespace ldetr
 
 using namespace ldetr;
 
-// Scratch memory for the in-kernel split-K reduction on the calling thread's current device.  `ptr` must be zero-filled
-// device memory that stays alive (and is used by one stream at a time); null/0 unregisters (atomic split-K path).
 extern "C" int ldetr_debug_trace_tiles(int64_t* buffer) {
     g_trace_buffer = reinterpret_cast<long long*>(buffer);
     return LDETR_OK;
@@ -1826,6 +1853,8 @@ extern "C" int ldetr_set_split_bf16(int tiles) {
     return prev;
 }
 
+// Scratch memory for the in-kernel split-K reduction on the calling thread's current device.  `ptr` must be zero-filled
+// device memory that stays alive (and is used by one stream at a time); null/0 unregisters (atomic split-K path).
 extern "C" int ldetr_set_workspace(void* ptr, int64_t bytes) {
     int dev = 0;
     LDETR_CHECK(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "set_workspace: no current device");
@@ -1842,34 +1871,37 @@ extern "C" int ldetr_set_workspace(void* ptr, int64_t bytes) {
 //   ta == 0: A is [M,K] row-major (lda);  ta == 1: A is stored [K,M] (lda)
 //   tb == 0: B is stored [N,K] row-major (ldb)  — i.e. nn.Linear weight layout [out,in];
 //   tb == 1: B is stored [K,N] (ldb)
-extern "C" int ldetr_gemm_f32(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb,
-                              float* C, int64_t ldc, int M, int N, int K, int splitk,
-                              const ldetr_epilogue* ep, int pix_per_sample, void* stream) {
-    LDETR_CHECK(A && B && C, "gemm: null pointer");
+static GemmParams fill_dense(const ldetr_gemm_desc& g) {
+    GemmParams p = new_params();
+    p.A.p = g.A; p.A.ld = g.lda; p.B.p = g.B; p.B.ld = g.ldb;
+    p.A.vec = al16(g.A) && (g.lda % 4 == 0) && (g.ta ? (g.M % 4 == 0) : (g.K % 4 == 0));
+    p.B.vec = al16(g.B) && (g.ldb % 4 == 0) && (g.tb ? (g.N % 4 == 0) : (g.K % 4 == 0));
+    p.M = g.M; p.N = g.N; p.K = g.K; p.C = g.C; p.ldc = g.ldc;
+    p.zmode = 0; p.splitk = 1; p.pstep = 1; p.nsamp = 1; p.pix_per_sample = g.pix_per_sample;
+    fill_epilogue(p.ep, g.ep);
+    return p;
+}
+
+static int gemm_dense(const ldetr_gemm_desc& g, void* stream) {
+    const int M = g.M, N = g.N, K = g.K, ta = g.ta, tb = g.tb;
+    LDETR_CHECK(g.A && g.B && g.C, "gemm: null pointer");
     LDETR_CHECK(M >= 0 && N >= 0 && K >= 0, "gemm: negative dimension");
     if (M == 0 || N == 0) return LDETR_OK;
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
-    p.A.p = A; p.A.ld = lda; p.B.p = B; p.B.ld = ldb;
-    p.A.vec = al16(A) && (lda % 4 == 0) && (ta ? (M % 4 == 0) : (K % 4 == 0));
-    p.B.vec = al16(B) && (ldb % 4 == 0) && (tb ? (N % 4 == 0) : (K % 4 == 0));
-    p.M = M; p.N = N; p.K = K; p.C = C; p.ldc = ldc;
-    p.zmode = 0; p.splitk = splitk < 1 ? 1 : splitk; p.pstep = 1; p.nsamp = 1;
-    p.pix_per_sample = pix_per_sample;
-    fill_epilogue(p.ep, ep);
+    GemmParams p = fill_dense(g);
+    p.splitk = g.splitk < 1 ? 1 : g.splitk;
     LDETR_CHECK(!(p.splitk > 1 && p.ep.accumulate && !epilogue_is_linear(p.ep)), "gemm: split-K + accumulate needs a linear epilogue");
     hipStream_t st = (hipStream_t)stream;
-    const bool auto_split = (splitk == 0);   // splitk: 0 = let the launch policy decide, 1 = never split, >1 = explicit
+    const bool auto_split = (g.splitk == 0);   // splitk: 0 = let the launch policy decide, 1 = never split, >1 = explicit
+    const bool small = auto_split && small_class(M, N, K);
     if (p.ep.a_rowsum) {
-        LDETR_CHECK(ta == 1 && lda == M, "gemm: a_rowsum needs ta == 1 and a packed A (lda == M)");
-        const bool small = auto_split && (long)cdiv(M, 64) * cdiv(N, 64) < SMALL_GEMM_TILES && (long)M * N * K <= SMALL_GEMM_MNK && tb;
-        if (!small) {   // not the kernel that folds the row sums in: one column-sum pass over A = [K, M]
-            int rc = ldetr_colsum_f32(A, p.ep.a_rowsum, 1, K, M, stream);
+        LDETR_CHECK(ta == 1 && g.lda == M, "gemm: a_rowsum needs ta == 1 and a packed A (lda == M)");
+        if (!(small && tb)) {   // not the kernel that folds the row sums in: one column-sum pass over A = [K, M]
+            int rc = ldetr_colsum_f32(g.A, p.ep.a_rowsum, 1, K, M, stream);
             if (rc) return rc;
             p.ep.a_rowsum = nullptr;
         }
     }
-    if (auto_split && (long)cdiv(M, 64) * cdiv(N, 64) < SMALL_GEMM_TILES && (long)M * N * K <= SMALL_GEMM_MNK) {
+    if (small) {
         if (!ta && !tb) return launch_small<0, 0>(p, st);
         if (!ta && tb) return launch_small<0, 1>(p, st);
         if (ta && tb) return launch_small<1, 1>(p, st);
@@ -1881,24 +1913,19 @@ extern "C" int ldetr_gemm_f32(const float* A, int64_t lda, int ta, const float* 
     return LDETR_ERR_UNSUPPORTED;
 }
 
+extern "C" int ldetr_gemm_f32(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb,
+                              float* C, int64_t ldc, int M, int N, int K, int splitk,
+                              const ldetr_epilogue* ep, int pix_per_sample, void* stream) {
+    const ldetr_gemm_desc g = {A, lda, ta, B, ldb, tb, C, ldc, M, N, K, splitk, ep, pix_per_sample};
+    return gemm_dense(g, stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Two dense GEMMs in one call (the data gradient dX = dY W and the weight gradient dW += dY^T X of a linear layer).  When both are
 // plain small-tile problems (the usual case on the transformers' token counts) they run as ONE launch of gemm_small_pair_kernel;
 // anything else falls back to two ldetr_gemm_f32 calls in order.  Same semantics either way.
 static bool small_class(const ldetr_gemm_desc& g) {
-    if (g.splitk != 0 || g.M <= 0 || g.N <= 0 || g.K <= 0) return false;
-    return (long)cdiv(g.M, 64) * cdiv(g.N, 64) < SMALL_GEMM_TILES && (long)g.M * g.N * g.K <= SMALL_GEMM_MNK;
-}
-
-static void fill_dense(GemmParams& p, const ldetr_gemm_desc& g) {
-    memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
-    p.A.p = g.A; p.A.ld = g.lda; p.B.p = g.B; p.B.ld = g.ldb;
-    p.A.vec = al16(g.A) && (g.lda % 4 == 0) && (g.ta ? (g.M % 4 == 0) : (g.K % 4 == 0));
-    p.B.vec = al16(g.B) && (g.ldb % 4 == 0) && (g.tb ? (g.N % 4 == 0) : (g.K % 4 == 0));
-    p.M = g.M; p.N = g.N; p.K = g.K; p.C = g.C; p.ldc = g.ldc;
-    p.zmode = 0; p.splitk = 1; p.pstep = 1; p.nsamp = 1; p.pix_per_sample = g.pix_per_sample;
-    fill_epilogue(p.ep, g.ep);
+    return g.splitk == 0 && g.M > 0 && g.N > 0 && g.K > 0 && small_class(g.M, g.N, g.K);
 }
 
 static bool pair_single_launch(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1) {
@@ -1916,48 +1943,13 @@ extern "C" int ldetr_gemm_pair_is_single_launch(const ldetr_gemm_desc* g0, const
 
 extern "C" int ldetr_gemm_pair_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1, void* stream) {
     LDETR_CHECK(g0 && g1, "gemm_pair: null descriptor");
-    if (pair_single_launch(g0, g1)) {
-        GemmParams p0, p1;
-        fill_dense(p0, *g0); fill_dense(p1, *g1);
-        const int gx0 = cdiv(p0.N, 32), nt0 = gx0 * cdiv(p0.M, 32), gx1 = cdiv(p1.N, 32), nt1 = gx1 * cdiv(p1.M, 32);
-        // one block size for both: 8 waves only when both problems would take them on their own
-        auto wants8 = [](long blocks, int sk, int K) { return blocks * sk <= 256 && (K + sk - 1) / sk >= 512; };
-        if (g0->ta == 1) {     // TN + TN
-            const int sk0 = plan_small_split(p0, nt0), sk1 = plan_small_split(p1, nt1);
-            const bool w8 = wants8(nt0, sk0, p0.K) && wants8(nt1, sk1, p1.K);
-            hipStream_t st = (hipStream_t)stream;
-            const dim3 grid((unsigned)(nt0 * sk0 + nt1 * sk1));
-            if (small_fast_ok(p0, 1, 1) && small_fast_ok(p1, 1, 1)) {
-                if (w8) hipLaunchKernelGGL((gemm_small_pair_kernel<1, 1, 1, 1, 8, true>), grid, 512, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-                else hipLaunchKernelGGL((gemm_small_pair_kernel<1, 1, 1, 1, 4, true>), grid, 256, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-            } else if (w8) hipLaunchKernelGGL((gemm_small_pair_kernel<1, 1, 1, 1, 8>), grid, 512, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-            else hipLaunchKernelGGL((gemm_small_pair_kernel<1, 1, 1, 1, 4>), grid, 256, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-            t_launches_f32++;
-            note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, (small_fast_ok(p0, 1, 1) && small_fast_ok(p1, 1, 1)) ? 1 : 0, 0, sk0 * 256 + sk1, (long)grid.x, 3 * 4 + 3);
-            return check_launch("gemm_small_pair");
-        }
-        if (!p0.ep.a_rowsum) {
-            const int sk0 = plan_small_split(p0, nt0), sk1 = plan_small_split(p1, nt1);
-            const bool w8 = wants8(nt0, sk0, p0.K) && wants8(nt1, sk1, p1.K);
-            hipStream_t st = (hipStream_t)stream;
-            const dim3 grid((unsigned)(nt0 * sk0 + nt1 * sk1));
-            if (small_fast_ok(p0, 0, 1) && small_fast_ok(p1, 1, 1)) {
-                if (w8) hipLaunchKernelGGL((gemm_small_pair_kernel<0, 1, 1, 1, 8, true>), grid, 512, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-                else hipLaunchKernelGGL((gemm_small_pair_kernel<0, 1, 1, 1, 4, true>), grid, 256, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-            } else if (w8) hipLaunchKernelGGL((gemm_small_pair_kernel<0, 1, 1, 1, 8>), grid, 512, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-            else hipLaunchKernelGGL((gemm_small_pair_kernel<0, 1, 1, 1, 4>), grid, 256, 0, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-            t_launches_f32++;
-            note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, (small_fast_ok(p0, 0, 1) && small_fast_ok(p1, 1, 1)) ? 1 : 0, 0, sk0 * 256 + sk1, (long)grid.x, 1 * 4 + 3);
-            return check_launch("gemm_small_pair");
-        }
+    if (pair_single_launch(g0, g1)) {   // (an NN first problem carries no row-sum output here: pair_single_launch)
+        GemmParams p0 = fill_dense(*g0), p1 = fill_dense(*g1);
+        return g0->ta == 1 ? launch_small_pair<1>(p0, p1, (hipStream_t)stream) : launch_small_pair<0>(p0, p1, (hipStream_t)stream);
     }
-    int rc = ldetr_gemm_f32(g0->A, g0->lda, g0->ta, g0->B, g0->ldb, g0->tb, g0->C, g0->ldc, g0->M, g0->N, g0->K, g0->splitk, g0->ep, g0->pix_per_sample, stream);
+    int rc = gemm_dense(*g0, stream);
     if (rc) return rc;
-    return ldetr_gemm_f32(g1->A, g1->lda, g1->ta, g1->B, g1->ldb, g1->tb, g1->C, g1->ldc, g1->M, g1->N, g1->K, g1->splitk, g1->ep, g1->pix_per_sample, stream);
-}
-
-static void set_conv_src(Operand& o, const float* x, const ldetr_tensor4* t) {
-    o.p = x; o.SH = t->H; o.SW = t->W; o.sn = t->sn; o.sh = t->sh; o.sw = t->sw; o.sc = t->sc;
+    return gemm_dense(*g1, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1979,26 +1971,21 @@ extern "C" int ldetr_conv2d_fwd_f32(const float* x, const ldetr_tensor4* xt, con
         if (took > 0) t_launches_f32++;
         if (took != 0) return took > 0 ? LDETR_OK : LDETR_ERR_LAUNCH;
     }
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
-    set_conv_src(p.A, x, xt);
-    p.A.DH = OH; p.A.DW = OW; p.A.C = xt->C; p.A.stride = stride; p.A.pad = pad; p.A.KH = KH; p.A.KW = KW;
-    p.A.scale = in_scale; p.A.scale_ld = in_scale_ld;
-    p.A.vec = (xt->sc == 1) && (xt->C % 4 == 0) && al16(x) && (xt->sn % 4 == 0) && (xt->sh % 4 == 0) && (xt->sw % 4 == 0) &&
-              (!in_scale || (al16(in_scale) && in_scale_ld % 4 == 0));
+    GemmParams p = new_params();
+    set_conv_operand(p.A, x, xt, in_scale, in_scale_ld, OH, OW, stride, pad, KH, KW);
+    p.A.C = xt->C;
+    p.A.vec = p.A.vec && (xt->sc == 1) && (xt->C % 4 == 0);
     long K = (long)KH * KW * xt->C;
     p.B.p = w; p.B.ld = K; p.B.vec = al16(w) && (K % 4 == 0);
     p.M = xt->N * OH * OW; p.N = Cout; p.K = (int)K; p.C = y; p.ldc = ldy;
     p.zmode = 0; p.splitk = 1; p.pstep = 1; p.nsamp = xt->N; p.pix_per_sample = OH * OW;
     fill_epilogue(p.ep, ep);
     hipStream_t st = (hipStream_t)stream;
-    if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && p.A.vec && !in_scale && xt->sw == xt->C && xt->sh == (long)xt->W * xt->C &&
-        xt->sn == (long)xt->H * xt->W * xt->C) {
+    if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && p.A.vec && !in_scale && packed_nhwc(xt)) {
         p.A.ld = xt->C;  // pure GEMM view of a packed NHWC tensor
         // few output tiles (the trunk's 1x1 convolutions at 2-4 samples per GPU: 32..128 tiles of 64x64 on 256 CUs): the latency-bound
         // small-tile kernel, like every other dense contraction of that class (ldetr_gemm_f32); same epilogue
-        if (!p.ep.samp_scale && (long)cdiv(p.M, 64) * cdiv(p.N, 64) < SMALL_GEMM_TILES && (long)p.M * p.N * p.K <= SMALL_GEMM_MNK)
-            return launch_small<0, 0>(p, st);
+        if (!p.ep.samp_scale && small_class(p.M, p.N, p.K)) return launch_small<0, 0>(p, st);
         return launch_gemm<OP_KC_DENSE, OP_KC_DENSE>(p, p.M, p.M, 1, true, false, st);
     }
     return launch_gemm<OP_KC_CONV, OP_KC_DENSE>(p, p.M, p.M, 1, true, false, st);
@@ -2017,13 +2004,9 @@ extern "C" int ldetr_conv2d_bwd_data_f32(const float* dy, const ldetr_tensor4* d
         if (took > 0) t_launches_f32++;
         if (took != 0) return took > 0 ? LDETR_OK : LDETR_ERR_LAUNCH;
     }
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
-    set_conv_src(p.A, dy, dyt);
-    p.A.DH = IH; p.A.DW = IW; p.A.C = dyt->C; p.A.stride = stride; p.A.pad = pad; p.A.KH = KH; p.A.KW = KW;
-    p.A.scale = dy_scale; p.A.scale_ld = dy_scale_ld;
-    p.A.vec = al16(dy) && (dyt->sn % 4 == 0) && (dyt->sh % 4 == 0) && (dyt->sw % 4 == 0) &&
-              (!dy_scale || (al16(dy_scale) && dy_scale_ld % 4 == 0));
+    GemmParams p = new_params();
+    set_conv_operand(p.A, dy, dyt, dy_scale, dy_scale_ld, IH, IW, stride, pad, KH, KW);
+    p.A.C = dyt->C;
     LDETR_CHECK(p.A.vec, "conv2d_bwd_data: dy must be 16-byte aligned NHWC");
     p.B.p = w; p.B.ld = (long)KH * KW * Cin; p.B.C = dyt->C; p.B.Cr = Cin; p.B.KH = KH; p.B.KW = KW;
     p.B.vec = al16(w);
@@ -2031,18 +2014,37 @@ extern "C" int ldetr_conv2d_bwd_data_f32(const float* dy, const ldetr_tensor4* d
     p.zmode = 1; p.splitk = 1; p.pstep = stride; p.nsamp = dyt->N; p.pix_per_sample = IH * IW;
     p.M = dyt->N * IH * IW; p.K = KH * KW * dyt->C;
     fill_epilogue(p.ep, ep);
-    {   // 1x1 / stride 1 on few output tiles (the trunk at 2-4 samples per GPU): dx[M, Cin] = (dy * scale)[M, Cout] . w[Cout, Cin] as a
-        // dense small-tile contraction over Cout, like the forward (ldetr_conv2d_fwd_f32)
-        if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && dyt->sw == dyt->C && dyt->sh == (long)dyt->W * dyt->C &&
-            dyt->sn == (long)dyt->H * dyt->W * dyt->C && (!dy_scale || dy_scale_ld == 0) && dyt->C % 4 == 0 && !p.ep.samp_scale &&
-            (long)cdiv(p.M, 64) * cdiv(p.N, 64) < SMALL_GEMM_TILES && (long)p.M * p.N * p.K <= SMALL_GEMM_MNK) {
-            GemmParams g = p;
-            g.zmode = 0; g.pstep = 1; g.A.ld = dyt->C; g.B.ld = Cin; g.B.vec = al16(w) && (Cin % 4 == 0);
-            return launch_small<0, 1>(g, (hipStream_t)stream);
-        }
+    // 1x1 / stride 1 on few output tiles (the trunk at 2-4 samples per GPU): dx[M, Cin] = (dy * scale)[M, Cout] . w[Cout, Cin] as a
+    // dense small-tile contraction over Cout, like the forward (ldetr_conv2d_fwd_f32)
+    if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && packed_nhwc(dyt) && (!dy_scale || dy_scale_ld == 0) && dyt->C % 4 == 0 &&
+        !p.ep.samp_scale && small_class(p.M, p.N, p.K)) {
+        GemmParams g = p;
+        g.zmode = 0; g.pstep = 1; g.A.ld = dyt->C; g.B.ld = Cin; g.B.vec = al16(w) && (Cin % 4 == 0);
+        return launch_small<0, 1>(g, (hipStream_t)stream);
     }
     int Mmax = dyt->N * cdiv(IH, stride) * cdiv(IW, stride);
     return launch_gemm<OP_KC_CONVT, OP_RC_WT>(p, Mmax, (long)p.M, stride * stride, true, false, (hipStream_t)stream);
+}
+
+// Shared start of the two weight-gradient entries (`splitk` already resolved by wgrad_auto_split): a problem with the neutral epilogue,
+// dw zeroed unless the gradient is added onto it, and the `accumulate` flag of an unsplit launch (a split one adds with atomics anyway).
+static int wgrad_begin(GemmParams& p, int splitk, int nsamp, float* dw, long wsz, int accumulate, hipStream_t st) {
+    p = new_params();
+    fill_epilogue(p.ep, nullptr);
+    p.splitk = splitk; p.pstep = 1; p.nsamp = nsamp; p.pix_per_sample = 0;
+    if (!accumulate) { if (int zrc = zero_fill(dw, wsz, wsz, 1, st)) return zrc; }
+    if (splitk == 1 && accumulate) p.ep.accumulate = 1;
+    return LDETR_OK;
+}
+
+// Per-sample scales (style modulation of x, demodulation of dy) on >= 64 pixels per sample: factor them out of the k-loop
+// (set_sample_slices); the operands then carry none.
+static void wgrad_factor_sample_scales(GemmParams& p, int nsamp, int pix_per_samp, int accumulate, const float*& dy_scale, long dy_scale_ld,
+                                       const float*& x_scale, long x_scale_ld) {
+    if (!((dy_scale || x_scale) && (!dy_scale || dy_scale_ld != 0) && (!x_scale || x_scale_ld != 0) && pix_per_samp >= 64)) return;
+    set_sample_slices(p, nsamp, pix_per_samp, p.splitk, dy_scale, dy_scale_ld, x_scale, x_scale_ld);
+    if (p.splitk == 1 && accumulate) p.ep.accumulate = 1;
+    dy_scale = nullptr; x_scale = nullptr;
 }
 
 // conv2d backward-weight: dw[co,kh,kw,ci] = sum_{n,oh,ow} dy[n,oh,ow,co] * x[n, oh*s-p+kh, ow*s-p+kw, ci].
@@ -2055,79 +2057,55 @@ extern "C" int ldetr_conv2d_bwd_weight_f32(const float* x, const ldetr_tensor4* 
     LDETR_CHECK(dyt->sc == 1, "conv2d_bwd_weight: dy must be NHWC");
     int Cin = xt->C, Cout = dyt->C, OH = dyt->H, OW = dyt->W;
     hipStream_t st = (hipStream_t)stream;
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
     int Kpix = dyt->N * OH * OW;
     const bool gather = (xt->sc != 1 || Cin % 4 != 0);
     if (splitk < 1)   // 0 = automatic
         splitk = gather ? wgrad_auto_split(Cout, KH * KW * Cin, Kpix, 1) : wgrad_auto_split(Cout, Cin, Kpix, KH * KW);
-    fill_epilogue(p.ep, nullptr);
-    p.splitk = splitk; p.pstep = 1; p.nsamp = xt->N; p.pix_per_sample = 0;
-    long wsz = (long)Cout * KH * KW * Cin;
-    if (!accumulate) { if (int zrc = zero_fill(dw, wsz, wsz, 1, st)) return zrc; }
+    GemmParams p;
+    if (int rc = wgrad_begin(p, splitk, xt->N, dw, (long)Cout * KH * KW * Cin, accumulate, st)) return rc;
     if (!gather) {   // 32 -> 32 channels on a large grid: the LDS-free operand-streaming kernel (wgrad_smallc.hip)
         const int took = try_launch_wgrad_smallc(x, xt, dy, dyt, dw, KH, KW, stride, pad, x_scale, x_scale_ld, dy_scale, dy_scale_ld, st);
         if (took > 0) t_launches_f32++;
         if (took != 0) return took > 0 ? LDETR_OK : LDETR_ERR_LAUNCH;
     }
-    if (splitk == 1 && accumulate) p.ep.accumulate = 1;
+    p.M = Cout; p.K = Kpix; p.C = dw; p.ldc = (long)KH * KW * Cin;
     if (gather) {
         // 3-channel (or strided-channel) input, e.g. the ResNet stem on an NCHW image: a single GEMM with
         // A = dy viewed [k = pixel][m = co] and B = scalar im2col gather [k = pixel][n = (tap, c)].
-        LDETR_CHECK(dyt->sw == Cout && dyt->sh == (long)OW * Cout && dyt->sn == (long)OH * OW * Cout, "conv2d_bwd_weight: dy must be packed NHWC");
+        LDETR_CHECK(packed_nhwc(dyt), "conv2d_bwd_weight: dy must be packed NHWC");
         LDETR_CHECK(!x_scale && !dy_scale, "conv2d_bwd_weight: scales unsupported on the scalar-gather path");
         p.A.p = dy; p.A.ld = Cout; p.A.vec = al16(dy) && (Cout % 4 == 0);
-        set_conv_src(p.B, x, xt);
+        set_conv_src(p.B, x, xt);   // (no vector loads on this view)
         p.B.DH = OH; p.B.DW = OW; p.B.C = Cin; p.B.stride = stride; p.B.pad = pad; p.B.KH = KH; p.B.KW = KW;
-        p.M = Cout; p.N = KH * KW * Cin; p.K = Kpix; p.C = dw; p.ldc = (long)KH * KW * Cin; p.zmode = 0;
+        p.N = KH * KW * Cin; p.zmode = 0;
         return launch_gemm<OP_RC_DENSE, OP_RC_CONVK>(p, p.M, p.M, 1, false, true, st);
     }
     // A = dy viewed as [k = pixel][m = co]; B = x gathered per tap [k = pixel][n = ci]
     if (dy_scale && dy_scale_ld == 0) { p.ep.row_scale = dy_scale; dy_scale = nullptr; }   // one scale per co for all samples: out of the k-loop
-    p.M = Cout; p.N = Cin; p.K = Kpix; p.C = dw; p.ldc = (long)KH * KW * Cin;
-    p.zmode = 2; p.ntaps = KH * KW; p.c_tap_stride = Cin;
-    if ((dy_scale || x_scale) && (!dy_scale || dy_scale_ld != 0) && (!x_scale || x_scale_ld != 0) && OH * OW >= 64) {
-        // per-sample scales (style modulation of x, demodulation of dy): factor them out of the k-loop
-        set_sample_slices(p, dyt->N, OH * OW, splitk, dy_scale, dy_scale_ld, x_scale, x_scale_ld);
-        if (p.splitk == 1 && accumulate) p.ep.accumulate = 1;
-        dy_scale = nullptr; x_scale = nullptr;
-    }
-    const bool dy_packed = !dy_scale && dyt->sw == Cout && dyt->sh == (long)OW * Cout && dyt->sn == (long)OH * OW * Cout;
-    if (dy_packed) {
+    p.N = Cin; p.zmode = 2; p.ntaps = KH * KW; p.c_tap_stride = Cin;
+    wgrad_factor_sample_scales(p, dyt->N, OH * OW, accumulate, dy_scale, dy_scale_ld, x_scale, x_scale_ld);
+    if (!dy_scale && packed_nhwc(dyt)) {
         // packed NHWC dy without per-sample scale is a plain [pixels, Cout] matrix: no pixel decode for that operand;
         // a 1x1 / stride 1 conv over packed x is a plain transposed GEMM altogether
         p.A.p = dy; p.A.ld = Cout; p.A.vec = al16(dy) && (Cout % 4 == 0);
-        const bool x_packed = !x_scale && KH == 1 && KW == 1 && stride == 1 && pad == 0 && xt->sw == Cin && xt->sh == (long)xt->W * Cin &&
-                              xt->sn == (long)xt->H * xt->W * Cin;
-        if (x_packed) {
+        if (!x_scale && KH == 1 && KW == 1 && stride == 1 && pad == 0 && packed_nhwc(xt)) {
             p.B.p = x; p.B.ld = Cin; p.B.vec = al16(x);
             // few output tiles and a short reduction (the trunk's 1x1 weight gradients at 2-4 samples per GPU): the small-tile kernel
             // (dw is zero or holds the running gradient at this point: accumulate; its own in-kernel split-K when the reduction is long)
-            if ((long)cdiv(p.M, 64) * cdiv(p.N, 64) < SMALL_GEMM_TILES && (long)p.M * p.N * p.K <= SMALL_GEMM_MNK && Kpix <= 8192) {
+            if (small_class(p.M, p.N, p.K) && Kpix <= 8192) {
                 p.zmode = 0; p.ntaps = 1; p.c_tap_stride = 0; p.splitk = 1; p.ep.accumulate = 1;
                 return launch_small<1, 1>(p, st);
             }
             return launch_gemm<OP_RC_DENSE, OP_RC_DENSE>(p, p.M, p.M, 1, false, true, st);
         }
-        set_conv_src(p.B, x, xt);
-        p.B.DH = OH; p.B.DW = OW; p.B.stride = stride; p.B.pad = pad; p.B.KH = KH; p.B.KW = KW; p.B.tapped = 1;
-        p.B.scale = x_scale; p.B.scale_ld = x_scale_ld;
-        p.B.vec = al16(x) && (xt->sn % 4 == 0) && (xt->sh % 4 == 0) && (xt->sw % 4 == 0) &&
-                  (!x_scale || (al16(x_scale) && x_scale_ld % 4 == 0));
+        set_conv_operand(p.B, x, xt, x_scale, x_scale_ld, OH, OW, stride, pad, KH, KW);
+        p.B.tapped = 1;
         return launch_gemm<OP_RC_DENSE, OP_RC_PIX>(p, p.M, p.M, p.ntaps, false, true, st);
     }
-    set_conv_src(p.A, dy, dyt);
-    p.A.DH = OH; p.A.DW = OW; p.A.stride = 1; p.A.pad = 0; p.A.tapped = 0;
-    p.A.scale = dy_scale; p.A.scale_ld = dy_scale_ld;
-    p.A.vec = al16(dy) && (Cout % 4 == 0) && (dyt->sn % 4 == 0) && (dyt->sh % 4 == 0) && (dyt->sw % 4 == 0) &&
-              (!dy_scale || (al16(dy_scale) && dy_scale_ld % 4 == 0));
-    set_conv_src(p.B, x, xt);
-    p.B.DH = OH; p.B.DW = OW; p.B.stride = stride; p.B.pad = pad; p.B.KH = KH; p.B.KW = KW; p.B.tapped = 1;
-    p.B.scale = x_scale; p.B.scale_ld = x_scale_ld;
-    p.B.vec = al16(x) && (xt->sn % 4 == 0) && (xt->sh % 4 == 0) && (xt->sw % 4 == 0) &&
-              (!x_scale || (al16(x_scale) && x_scale_ld % 4 == 0));
-    p.M = Cout; p.N = Cin; p.K = Kpix; p.C = dw; p.ldc = (long)KH * KW * Cin;
-    p.zmode = 2; p.ntaps = KH * KW; p.c_tap_stride = Cin;
+    set_conv_operand(p.A, dy, dyt, dy_scale, dy_scale_ld, OH, OW, 1, 0, 1, 1);
+    p.A.vec = p.A.vec && (Cout % 4 == 0);
+    set_conv_operand(p.B, x, xt, x_scale, x_scale_ld, OH, OW, stride, pad, KH, KW);
+    p.B.tapped = 1;
     return launch_gemm<OP_RC_PIX, OP_RC_PIX>(p, p.M, p.M, p.ntaps, false, true, st);
 }
 
@@ -2141,13 +2119,9 @@ extern "C" int ldetr_conv_transpose2d_fwd_f32(const float* x, const ldetr_tensor
     LDETR_CHECK(xt->sc == 1 && xt->C % 4 == 0, "conv_transpose2d_fwd: x must be NHWC with C % 4 == 0");
     int eOH = (xt->H - 1) * stride - 2 * pad + KH, eOW = (xt->W - 1) * stride - 2 * pad + KW;
     LDETR_CHECK(eOH == OH && eOW == OW, "conv_transpose2d_fwd: output size mismatch (expected %dx%d)", eOH, eOW);
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
-    set_conv_src(p.A, x, xt);
-    p.A.DH = OH; p.A.DW = OW; p.A.C = xt->C; p.A.stride = stride; p.A.pad = pad; p.A.KH = KH; p.A.KW = KW;
-    p.A.scale = in_scale; p.A.scale_ld = in_scale_ld;
-    p.A.vec = al16(x) && (xt->sn % 4 == 0) && (xt->sh % 4 == 0) && (xt->sw % 4 == 0) &&
-              (!in_scale || (al16(in_scale) && in_scale_ld % 4 == 0));
+    GemmParams p = new_params();
+    set_conv_operand(p.A, x, xt, in_scale, in_scale_ld, OH, OW, stride, pad, KH, KW);
+    p.A.C = xt->C;
     LDETR_CHECK(p.A.vec, "conv_transpose2d_fwd: x must be 16-byte aligned NHWC");
     p.B.p = w; p.B.ld = (long)KH * KW * xt->C; p.B.C = xt->C; p.B.KH = KH; p.B.KW = KW; p.B.vec = al16(w);
     LDETR_CHECK(p.B.vec, "conv_transpose2d_fwd: w must be 16-byte aligned");
@@ -2166,13 +2140,9 @@ extern "C" int ldetr_conv_transpose2d_bwd_data_f32(const float* dy, const ldetr_
                                                    const ldetr_epilogue* ep, void* stream) {
     LDETR_CHECK(dy && w && dx && dyt, "conv_transpose2d_bwd_data: null pointer");
     LDETR_CHECK(dyt->sc == 1 && dyt->C % 4 == 0 && Cin % 4 == 0, "conv_transpose2d_bwd_data: channels must be NHWC multiples of 4");
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
-    set_conv_src(p.A, dy, dyt);
-    p.A.DH = IH; p.A.DW = IW; p.A.C = dyt->C; p.A.stride = stride; p.A.pad = pad; p.A.KH = KH; p.A.KW = KW;
-    p.A.scale = dy_scale; p.A.scale_ld = dy_scale_ld;
-    p.A.vec = al16(dy) && (dyt->sn % 4 == 0) && (dyt->sh % 4 == 0) && (dyt->sw % 4 == 0) &&
-              (!dy_scale || (al16(dy_scale) && dy_scale_ld % 4 == 0));
+    GemmParams p = new_params();
+    set_conv_operand(p.A, dy, dyt, dy_scale, dy_scale_ld, IH, IW, stride, pad, KH, KW);
+    p.A.C = dyt->C;
     LDETR_CHECK(p.A.vec, "conv_transpose2d_bwd_data: dy must be 16-byte aligned NHWC");
     p.B.p = w; p.B.ld = (long)KH * KW * Cin; p.B.C = dyt->C; p.B.Cr = Cin; p.B.KH = KH; p.B.KW = KW; p.B.vec = al16(w);
     p.M = dyt->N * IH * IW; p.N = Cin; p.K = KH * KW * dyt->C; p.C = dx; p.ldc = lddx;
@@ -2190,33 +2160,17 @@ extern "C" int ldetr_conv_transpose2d_bwd_weight_f32(const float* x, const ldetr
     LDETR_CHECK(dyt->sc == 1 && xt->sc == 1 && xt->C % 4 == 0 && dyt->C % 4 == 0, "conv_transpose2d_bwd_weight: NHWC, C % 4 == 0 required");
     int Cin = xt->C, Cout = dyt->C;
     hipStream_t st = (hipStream_t)stream;
-    GemmParams p; memset(&p, 0, sizeof(p));
-    init_operand(p.A); init_operand(p.B);
     if (splitk < 1) splitk = wgrad_auto_split(Cout, Cin, xt->N * xt->H * xt->W, KH * KW);   // 0 = automatic
-    fill_epilogue(p.ep, nullptr);
-    p.splitk = splitk; p.pstep = 1; p.nsamp = xt->N; p.pix_per_sample = 0;
-    long wsz = (long)Cout * KH * KW * Cin;
-    if (!accumulate) { if (int zrc = zero_fill(dw, wsz, wsz, 1, st)) return zrc; }
-    if (splitk == 1 && accumulate) p.ep.accumulate = 1;
-    if ((dy_scale || x_scale) && (!dy_scale || dy_scale_ld != 0) && (!x_scale || x_scale_ld != 0) && xt->H * xt->W >= 64) {
-        set_sample_slices(p, xt->N, xt->H * xt->W, splitk, dy_scale, dy_scale_ld, x_scale, x_scale_ld);   // scales out of the k-loop
-        if (p.splitk == 1 && accumulate) p.ep.accumulate = 1;
-        dy_scale = nullptr; x_scale = nullptr;
-    }
+    GemmParams p;
+    if (int rc = wgrad_begin(p, splitk, xt->N, dw, (long)Cout * KH * KW * Cin, accumulate, st)) return rc;
+    wgrad_factor_sample_scales(p, xt->N, xt->H * xt->W, accumulate, dy_scale, dy_scale_ld, x_scale, x_scale_ld);
     // k enumerates *input* pixels (n, ih, iw); A = dy gathered at (ih*s + kh - p, iw*s + kw - p), B = x dense.
-    set_conv_src(p.A, dy, dyt);
-    p.A.DH = xt->H; p.A.DW = xt->W; p.A.stride = stride; p.A.pad = pad; p.A.KH = KH; p.A.KW = KW; p.A.tapped = 1;
-    p.A.scale = dy_scale; p.A.scale_ld = dy_scale_ld;
-    p.A.vec = al16(dy) && (dyt->sn % 4 == 0) && (dyt->sh % 4 == 0) && (dyt->sw % 4 == 0) &&
-              (!dy_scale || (al16(dy_scale) && dy_scale_ld % 4 == 0));
-    set_conv_src(p.B, x, xt);
-    p.B.DH = xt->H; p.B.DW = xt->W; p.B.stride = 1; p.B.pad = 0; p.B.tapped = 0;
-    p.B.scale = x_scale; p.B.scale_ld = x_scale_ld;
-    p.B.vec = al16(x) && (xt->sn % 4 == 0) && (xt->sh % 4 == 0) && (xt->sw % 4 == 0) &&
-              (!x_scale || (al16(x_scale) && x_scale_ld % 4 == 0));
+    set_conv_operand(p.A, dy, dyt, dy_scale, dy_scale_ld, xt->H, xt->W, stride, pad, KH, KW);
+    p.A.tapped = 1;
     p.M = Cout; p.N = Cin; p.K = xt->N * xt->H * xt->W; p.C = dw; p.ldc = (long)KH * KW * Cin;
     p.zmode = 2; p.ntaps = KH * KW; p.c_tap_stride = Cin;
-    if (!x_scale && xt->sw == Cin && xt->sh == (long)xt->W * Cin && xt->sn == (long)xt->H * xt->W * Cin) {
+    set_conv_operand(p.B, x, xt, x_scale, x_scale_ld, xt->H, xt->W, 1, 0, 1, 1);
+    if (!x_scale && packed_nhwc(xt)) {
         p.B.p = x; p.B.ld = Cin; p.B.vec = al16(x);   // packed x: a plain [pixels, Cin] matrix
         return launch_gemm<OP_RC_PIX, OP_RC_DENSE>(p, p.M, p.M, p.ntaps, false, true, st);
     }

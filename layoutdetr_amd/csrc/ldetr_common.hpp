@@ -11,6 +11,9 @@
 #define LDETR_ERR_LAUNCH 2
 #define LDETR_ERR_UNSUPPORTED 3
 
+struct ldetr_tensor4;    // include/ldetr_hip.h
+struct ldetr_epilogue;
+
 namespace ldetr {
 
 void set_error(const char* fmt, ...);
@@ -26,10 +29,27 @@ double knob_f(const char* key, double dflt);
 // 4 conv3x3_c32(_split)_kernel, 5 wgrad_c32_3x3_kernel, 6 stem_conv7x7_kernel.  The parity tests assert the template a bench shape reaches and bench.py
 // labels its per-launch records with it.
 void note_engine_launch(int kind, int bm, int bn, int bk, int waves, int fast, int split, int splitk, long blocks, int modes);
+// One more contraction kernel issued by the calling thread, by matrix pipe (ldetr_engine_launch_counts; defined in gemm_conv.hip): the contraction
+// kernels of the other translation units (p3_engine.hip, mha_small.hip, ffn_fused.hip) count themselves through it.
+void count_engine_launch(bool bf16_split_pipe);
 
-// Slice of the caller-registered workspace (ldetr_set_workspace) for the launches enqueued next; nullptr if unavailable.
-// Defined in gemm_conv.hip next to the split-K ring it shares.
+// The workspace registered with ldetr_set_workspace is handed out as rings, one fresh slice per launch (all three defined in gemm_conv.hip).
+// scratch_alloc: transient scratch for the launches enqueued next; nullptr if unavailable.
+// splitk_ws_alloc: `tiles` arrival counters + `partial_bytes` of partial tiles for a split-K launch; false if unavailable.
 float* scratch_alloc(size_t bytes);
+bool splitk_ws_alloc(long tiles, size_t partial_bytes, float** ws, int** counters);
+// The bf16 pipe with the exact operand split is on (ldetr_set_split_bf16 / LDETR_DEBUG="SPLIT_BF16=0"): conv_c32.hip follows the engine's switch.
+bool engine_split_enabled();
+
+// Kernels of their own that the engine's convolution entries try first (stem_conv.hip, conv_c32.hip, wgrad_smallc.hip); return conventions at the
+// definitions.
+int try_launch_stem_conv(const float* x, const ldetr_tensor4* xt, const float* w, int Cout, int KH, int KW, int stride, int pad,
+                         float* y, long ldy, int OH, int OW, const float* in_scale, const ldetr_epilogue* ep, hipStream_t st);
+int try_launch_conv_c32(const float* x, const ldetr_tensor4* xt, const float* w, int Cout, int KH, int KW, int stride, int pad,
+                        float* y, long ldy, int OH, int OW, const float* k_scale, long k_scale_ld, const ldetr_epilogue* ep,
+                        int transposed, hipStream_t st);
+int try_launch_wgrad_smallc(const float* x, const ldetr_tensor4* xt, const float* dy, const ldetr_tensor4* dyt, float* dw, int KH, int KW, int stride, int pad,
+                            const float* x_scale, int64_t x_scale_ld, const float* dy_scale, int64_t dy_scale_ld, hipStream_t st);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

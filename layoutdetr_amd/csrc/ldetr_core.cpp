@@ -6,9 +6,8 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include "ldetr_common.hpp"
 #include "../../include/ldetr_hip.h"
-
-namespace ldetr { void note_engine_launch(int kind, int bm, int bn, int bk, int waves, int fast, int split, int splitk, long blocks, int modes); }
 
 namespace ldetr {
 static thread_local char g_err[512] = "";

@@ -24,9 +24,6 @@
 
 namespace ldetr {
 
-bool splitk_ws_alloc(long tiles, size_t partial_bytes, float** ws, int** counters);   // gemm_conv.hip (ring of ldetr_set_workspace)
-void note_engine_launch(bool bf16_split_pipe);                                          // gemm_conv.hip (ldetr_engine_launch_counts)
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
@@ -1225,7 +1222,7 @@ static int launch_nt_cfg(P3NtParams& p, const P3Group2& g2, int sk, hipStream_t 
             if (!raise_lds(reinterpret_cast<const void*>(kern1), g.lds, "p3_nt", raised1)) return LDETR_ERR_LAUNCH;
             hipLaunchKernelGGL(kern1, dim3((unsigned)g.gx, g.sk, g.ncls), NW * 64, g.lds, st, p, g2);
             t_last = {1, BM, BN, NW, g.sk, p.xm, p.xn, g.ncls, 0, g.gx};
-            note_engine_launch(true);
+            count_engine_launch(true);
             return check_launch("p3_nt");
         }
     }
@@ -1234,7 +1231,7 @@ static int launch_nt_cfg(P3NtParams& p, const P3Group2& g2, int sk, hipStream_t 
     if (!raise_lds(reinterpret_cast<const void*>(kern), g.lds, "p3_nt", raised)) return LDETR_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3((unsigned)g.gx, g.sk, g.ncls), NW * 64, g.lds, st, p, g2);
     t_last = {1, BM, BN, NW, g.sk, p.xm, p.xn, g.ncls, 0, g.gx};
-    note_engine_launch(true);
+    count_engine_launch(true);
     return check_launch("p3_nt");
 }
 
@@ -1298,7 +1295,7 @@ static int launch_c3(P3C3Params& p, const P3Group2& g2, hipStream_t st) {
     if (!raise_lds(reinterpret_cast<const void*>(&p3_c3_kernel), C3_LDS, "p3_c3", raised)) return LDETR_ERR_LAUNCH;
     hipLaunchKernelGGL(p3_c3_kernel, dim3((unsigned)grid_x, p.splitk, p.ngroups > 1 ? p.ngroups : 1), 256, C3_LDS, st, p, g2);
     t_last = {2, 128, 64, 4, p.splitk, p.xm, p.xn, p.ngroups > 1 ? p.ngroups : 1, 0, grid_x};
-    note_engine_launch(true);
+    count_engine_launch(true);
     return check_launch("p3_c3");
 }
 
@@ -1334,7 +1331,7 @@ static int launch_tn_cfg(P3TnParams& p, int target_blocks, hipStream_t st) {
     if (!raise_lds(reinterpret_cast<const void*>(kern), lds, "p3_tn", raised)) return LDETR_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(p.splitk, (unsigned)nt, 1), 256, lds, st, p);
     t_last = {3, BM, BN, 4, 0, 0, 0, 1, p.splitk, nt};
-    note_engine_launch(true);
+    count_engine_launch(true);
     return check_launch("p3_tn");
 }
 
@@ -1563,7 +1560,7 @@ extern "C" int ldetr_p3_conv2d_bwd_pair(const void* dy, int N, int OH, int OW, i
                                    (int)g.gx, g.sk);
             t_last = {4, 64, 64, 4, g.sk, pn.xm, pn.xn, g.ncls, pt.splitk, n_tn_pad + g.gx * g.sk * g.ncls};
         }
-        note_engine_launch(true);
+        count_engine_launch(true);
         if (launches) *launches = 1;
         return check_launch("p3_bwd_pair");
     }

@@ -88,10 +88,10 @@ class _ModConvFn(torch.autograd.Function):
                 dw_ohwi, acc = gw.permute(0, 2, 3, 1), 1
             else:
                 dw_ohwi = torch.empty((O, KH, KW, I), device=dy.device, dtype=torch.float32)
-            xt = core.tensor4_nhwc(x)
             sk = 0   # the library picks tile and split-K factor together
             xw, dvw, sw, dw_ = _prescaled_for_wgrad(x, dv, s, d, B, H)
-            core.engine_call('ldetr_conv2d_bwd_weight_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xt), core.ptr(dvw), ctypes.byref(dvt),
+            xwt, dvwt = core.tensor4_nhwc(xw), core.tensor4_nhwc(dvw)     # descriptors of the tensors actually passed
+            core.engine_call('ldetr_conv2d_bwd_weight_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xwt), core.ptr(dvw), ctypes.byref(dvwt),
                                                               core.ptr(dw_ohwi), KH, KW, 1, pad, sk, core.ptr(sw), sw.stride(0) if sw is not None else 0,
                                                               core.ptr(dw_), dw_.stride(0) if dw_ is not None else 0, acc, core.stream()), 'modconv_bwd_weight'), operands=(x, dv, dw_ohwi))
             dw = None if acc else _grad_to_oihw(dw_ohwi)
@@ -153,10 +153,10 @@ class _ModConvUpFn(torch.autograd.Function):
                 dw_ohwi, acc = gw.permute(0, 2, 3, 1), 1
             else:
                 dw_ohwi = torch.empty((O, KH, KW, I), device=dy.device, dtype=torch.float32)
-            xt = core.tensor4_nhwc(x)
             sk = 0   # the library picks tile and split-K factor together
             xw, dudw, sw, dw_ = _prescaled_for_wgrad(x, dud, s, d, B, H)
-            core.engine_call('ldetr_conv_transpose2d_bwd_weight_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xt), core.ptr(dudw), ctypes.byref(dudt),
+            xwt, dudwt = core.tensor4_nhwc(xw), core.tensor4_nhwc(dudw)   # descriptors of the tensors actually passed
+            core.engine_call('ldetr_conv_transpose2d_bwd_weight_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xwt), core.ptr(dudw), ctypes.byref(dudwt),
                                                                         core.ptr(dw_ohwi), KH, KW, 2, 0, sk, core.ptr(sw), sw.stride(0) if sw is not None else 0,
                                                                         core.ptr(dw_), dw_.stride(0) if dw_ is not None else 0, acc, core.stream()), 'modconv_up_bwd_weight'), operands=(x, dud, dw_ohwi))
             dw = None if acc else _grad_to_oihw(dw_ohwi)

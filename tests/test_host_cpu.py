@@ -610,6 +610,94 @@ def test_p3_entry_points_validate_before_launching():
     assert lib.ldetr_p3_split_f32(P(64), 16, P(64), 0, 16, None) == 0                                         # empty input
 
 
+def test_engine_entries_validate_before_launching():
+    """The C entry points of the fp32-operand engine (host part of csrc/gemm_conv.hip) check pointers, layouts and sizes before anything touches
+    the device: every message as it stands, through paths that return before the first HIP call."""
+    import ctypes
+    from layoutdetr_amd import _lib
+    lib = _lib.load()
+    P = ctypes.c_void_p
+    p = P(64)                                     # a non-NULL 16-byte aligned address: nothing is dereferenced on the host
+    t4 = lambda N=1, C=8, H=8, W=8, sc=1: ctypes.byref(_lib.Tensor4(N, C, H, W, H * W * C, sc, W * C, C))
+
+    def fails(rc, message):
+        assert rc != 0 and lib.ldetr_last_error() == message, (rc, lib.ldetr_last_error())
+    fails(lib.ldetr_gemm_f32(None, 8, 0, p, 8, 0, p, 8, 8, 8, 8, 0, None, 0, None), b'gemm: null pointer')
+    fails(lib.ldetr_gemm_f32(p, 8, 0, p, 8, 0, None, 8, 8, 8, 8, 0, None, 0, None), b'gemm: null pointer')
+    fails(lib.ldetr_gemm_f32(p, 8, 0, p, 8, 0, p, 8, -1, 8, 8, 0, None, 0, None), b'gemm: negative dimension')
+    fails(lib.ldetr_gemm_f32(p, 8, 0, p, 8, 0, p, 8, 8, 8, -8, 0, None, 0, None), b'gemm: negative dimension')
+    assert lib.ldetr_gemm_f32(p, 8, 0, p, 8, 0, p, 8, 0, 8, 8, 0, None, 0, None) == 0                       # M == 0: nothing to do
+    assert lib.ldetr_gemm_f32(p, 8, 1, p, 8, 1, p, 8, 8, 0, 8, 0, None, 0, None) == 0                       # N == 0
+    fails(lib.ldetr_conv2d_fwd_f32(p, None, p, 8, 3, 3, 1, 1, p, 8, 8, 8, None, 0, None, None), b'conv2d_fwd: null pointer')
+    fails(lib.ldetr_conv2d_fwd_f32(p, t4(), p, 8, 3, 3, 1, 1, p, 8, 8, 9, None, 0, None, None), b'conv2d_fwd: output size mismatch (expected 8x8)')
+    fails(lib.ldetr_conv2d_fwd_f32(p, t4(H=9, W=7), p, 8, 3, 3, 2, 1, p, 8, 5, 5, None, 0, None, None), b'conv2d_fwd: output size mismatch (expected 5x4)')
+    fails(lib.ldetr_conv2d_bwd_data_f32(None, t4(), p, 8, 3, 3, 1, 1, p, 8, 8, 8, None, 0, None, None), b'conv2d_bwd_data: null pointer')
+    for bad in (t4(sc=2), t4(C=6)):
+        fails(lib.ldetr_conv2d_bwd_data_f32(p, bad, p, 8, 3, 3, 1, 1, p, 8, 8, 8, None, 0, None, None),
+              b'conv2d_bwd_data: channels must be NHWC-contiguous multiples of 4')
+    fails(lib.ldetr_conv2d_bwd_data_f32(p, t4(), p, 6, 3, 3, 1, 1, p, 6, 8, 8, None, 0, None, None),
+          b'conv2d_bwd_data: channels must be NHWC-contiguous multiples of 4')
+    fails(lib.ldetr_conv2d_bwd_weight_f32(p, t4(), p, None, p, 3, 3, 1, 1, 0, None, 0, None, 0, 0, None), b'conv2d_bwd_weight: null pointer')
+    fails(lib.ldetr_conv2d_bwd_weight_f32(p, t4(), p, t4(sc=2), p, 3, 3, 1, 1, 0, None, 0, None, 0, 0, None), b'conv2d_bwd_weight: dy must be NHWC')
+    fails(lib.ldetr_conv_transpose2d_fwd_f32(p, t4(), None, 8, 3, 3, 2, 0, p, 8, 17, 17, None, 0, None, None), b'conv_transpose2d_fwd: null pointer')
+    for bad in (t4(sc=2), t4(C=6)):
+        fails(lib.ldetr_conv_transpose2d_fwd_f32(p, bad, p, 8, 3, 3, 2, 0, p, 8, 17, 17, None, 0, None, None),
+              b'conv_transpose2d_fwd: x must be NHWC with C % 4 == 0')
+    fails(lib.ldetr_conv_transpose2d_fwd_f32(p, t4(), p, 8, 3, 3, 2, 0, p, 8, 16, 17, None, 0, None, None),
+          b'conv_transpose2d_fwd: output size mismatch (expected 17x17)')
+    fails(lib.ldetr_conv_transpose2d_bwd_data_f32(p, t4(), p, 8, 3, 3, 2, 0, None, 8, 3, 3, None, 0, None, None), b'conv_transpose2d_bwd_data: null pointer')
+    fails(lib.ldetr_conv_transpose2d_bwd_data_f32(p, t4(), p, 6, 3, 3, 2, 0, p, 6, 3, 3, None, 0, None, None),
+          b'conv_transpose2d_bwd_data: channels must be NHWC multiples of 4')
+    fails(lib.ldetr_conv_transpose2d_bwd_weight_f32(None, t4(), p, t4(), p, 3, 3, 2, 0, 0, None, 0, None, 0, 0, None), b'conv_transpose2d_bwd_weight: null pointer')
+    for xt, dyt in ((t4(C=6), t4()), (t4(), t4(C=6)), (t4(sc=2), t4()), (t4(), t4(sc=2))):
+        fails(lib.ldetr_conv_transpose2d_bwd_weight_f32(p, xt, p, dyt, p, 3, 3, 2, 0, 0, None, 0, None, 0, 0, None),
+              b'conv_transpose2d_bwd_weight: NHWC, C % 4 == 0 required')
+    d = _lib.GemmDesc()
+    fails(lib.ldetr_gemm_pair_f32(None, ctypes.byref(d), None), b'gemm_pair: null descriptor')
+    fails(lib.ldetr_gemm_pair_f32(ctypes.byref(d), None, None), b'gemm_pair: null descriptor')
+
+
+def test_gemm_pair_single_launch_predicate():
+    """ldetr_gemm_pair_is_single_launch (pure host code): the two instantiated pairings at the transformers' token counts run as one launch;
+    anything that is not a plain small-tile problem of those layouts, or a row-sum output the pair kernel cannot fold in, takes two calls."""
+    import ctypes
+    from layoutdetr_amd import _lib
+    lib = _lib.load()
+    ep_rowsum = _lib.Epilogue()
+    ep_rowsum.alpha = 1.0; ep_rowsum.out_scale = 1.0; ep_rowsum.act_gain = 1.0; ep_rowsum.a_rowsum = 4096
+    ep_plain = _lib.Epilogue()
+    ep_plain.alpha = 1.0; ep_plain.out_scale = 1.0; ep_plain.act_gain = 1.0
+
+    def desc(ta, tb, M, N, K, splitk=0, B=0x2000, lda=None, ep=None):
+        g = _lib.GemmDesc()
+        g.A, g.B, g.C = 0x1000, B, 0x3000          # fake 16-byte aligned addresses: the predicate reads no memory
+        g.ta, g.tb, g.M, g.N, g.K, g.splitk = ta, tb, M, N, K, splitk
+        g.lda = lda if lda is not None else (M if ta else K)
+        g.ldb = N if tb else K
+        g.ldc = N
+        g.ep = ctypes.addressof(ep) if ep is not None else None
+        return g
+
+    def single(g0, g1):
+        return lib.ldetr_gemm_pair_is_single_launch(ctypes.byref(g0), ctypes.byref(g1))
+    nn, tn = (0, 1), (1, 1)                         # dX = dY W (A row-major, B stored [K, N]); dW = dY^T X
+    assert single(desc(*nn, 144, 256, 256), desc(*tn, 256, 256, 144)) == 1
+    assert single(desc(*tn, 2048, 256, 144), desc(*tn, 256, 2048, 144)) == 1
+    assert single(desc(1, 0, 144, 256, 256), desc(*tn, 256, 256, 144)) == 0                       # (ta = 1, tb = 0) is not a pairing
+    assert single(desc(*nn, 144, 256, 256, splitk=2), desc(*tn, 256, 256, 144)) == 0
+    assert single(desc(*nn, 144, 256, 256), desc(*tn, 256, 256, 144, splitk=2)) == 0
+    assert single(desc(*nn, 144, 256, 256), desc(*tn, 4096, 1024, 512)) == 0                      # 1024 tiles of 64 x 64: not the small class
+    assert single(desc(*nn, 144, 256, 256, B=None), desc(*tn, 256, 256, 144)) == 0
+    assert single(desc(*nn, 144, 256, 256), desc(*tn, 256, 256, 144, B=None)) == 0
+    assert single(desc(*nn, 144, 256, 256), desc(*tn, 256, 256, 144, ep=ep_rowsum)) == 1          # packed A: the kernel folds the row sums in
+    assert single(desc(*nn, 144, 256, 256), desc(*tn, 256, 256, 144, lda=260, ep=ep_rowsum)) == 0
+    assert single(desc(*nn, 144, 256, 256, ep=ep_rowsum), desc(*tn, 256, 256, 144)) == 0          # row sums need a transposed A
+    assert single(desc(*tn, 2048, 256, 144, ep=ep_rowsum), desc(*tn, 256, 2048, 144)) == 1
+    assert single(desc(*tn, 2048, 256, 144, lda=2052, ep=ep_rowsum), desc(*tn, 256, 2048, 144)) == 0
+    assert single(desc(*nn, 144, 256, 256, ep=ep_plain), desc(*tn, 256, 256, 144, ep=ep_plain)) == 1
+    assert lib.ldetr_gemm_pair_is_single_launch(None, None) == 0
+
+
 def test_backward_stage_count_and_two_stage_segments(monkeypatch):
     """training_loop.backward_stage_count (trunk | rest at <= 4 samples per GPU, three stages above, LDETR_BACKWARD_STAGES overrides) and
     FlatModule.stage_segments(2): the two-stage segments tile the flat buffer and merge the three-stage trunk segments."""
