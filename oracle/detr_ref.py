@@ -12,7 +12,11 @@ CPU fp32 restatement of the DETR pieces of the hot path, written as pure functio
   FrozenBatchNorm2d                      training/detr_backbone.py:55-65
   ResNet-50 v1.5 trunk                   torchvision==0.13.1 resnet50 (third-party; absent here: restated from
                                          its published architecture; PARITY UNPINNED by any reference vector)
-Dropout is the identity here (eval-mode parity; see DESIGN.md for the statistical dropout checks).
+Dropout is the identity by default (eval-mode parity).  mha / encoder_layer / decoder_layer / torch_encoder take an optional `drop`, a callable
+drop(site, tensor) -> tensor that applies an explicit mask at the reference's dropout positions (train-mode parity with the masks of
+oracle/dropout_ref.py): site = layer prefix + place, the places being 'attn' / 'cross' (the softmax probabilities [B*nhead, Lq, Lk],
+before p @ v), 'res1' / 'res2' / 'res3' (a sub-block's output incl. its bias [L, B, E], before the residual add) and 'hidden' (the feed-forward
+hidden activation [L, B, F], after the relu).
 Pinned by tests/test_oracle_golden.py against tests/golden/{transformer,transformer_token,
 transformer_layoutganpp,pos_encoding,frozen_bn}.npz.
 """
@@ -22,8 +26,8 @@ import torch
 import torch.nn.functional as F
 
 
-def mha(sd, pre, query, key, value, nhead, key_padding_mask=None):
-    """Seq-first [L, B, E] tensors, like the reference."""
+def mha(sd, pre, query, key, value, nhead, key_padding_mask=None, drop=None, site='attn'):
+    """Seq-first [L, B, E] tensors, like the reference.  drop(site, p): dropout on the probabilities p [B*nhead, Lq, Lk] (index b*nhead + h)."""
     Lq, B, E = query.shape
     Lk = key.shape[0]
     dh = E // nhead
@@ -38,6 +42,8 @@ def mha(sd, pre, query, key, value, nhead, key_padding_mask=None):
     if key_padding_mask is not None:
         s = s.view(B, nhead, Lq, Lk).masked_fill(key_padding_mask[:, None, None, :], float('-inf')).view(B * nhead, Lq, Lk)
     p = s.softmax(-1)
+    if drop is not None:
+        p = drop(site, p)
     o = torch.bmm(p, v).transpose(0, 1).reshape(Lq, B, E)
     return F.linear(o, sd[pre + 'out_proj.weight'], sd[pre + 'out_proj.bias'])
 
@@ -46,18 +52,30 @@ def _ln(sd, pre, x):
     return F.layer_norm(x, (x.shape[-1],), sd[pre + 'weight'], sd[pre + 'bias'], 1e-5)
 
 
-def _ffn(sd, pre, x):
+def _ffn(sd, pre, x, drop=None):
     h = F.relu(F.linear(x, sd[pre + 'linear1.weight'], sd[pre + 'linear1.bias']))
+    if drop is not None:
+        h = drop(pre + 'hidden', h)
     return F.linear(h, sd[pre + 'linear2.weight'], sd[pre + 'linear2.bias'])
 
 
-def encoder_layer(sd, pre, src, nhead, key_padding_mask, pos):
+def encoder_layer(sd, pre, src, nhead, key_padding_mask, pos, drop=None):
     qk = src if pos is None else src + pos
+    if drop is not None:
+        a = mha(sd, pre + 'self_attn.', qk, qk, src, nhead, key_padding_mask, drop, pre + 'attn')
+        src = _ln(sd, pre + 'norm1.', src + drop(pre + 'res1', a))
+        return _ln(sd, pre + 'norm2.', src + drop(pre + 'res2', _ffn(sd, pre, src, drop)))
     src = _ln(sd, pre + 'norm1.', src + mha(sd, pre + 'self_attn.', qk, qk, src, nhead, key_padding_mask))
     return _ln(sd, pre + 'norm2.', src + _ffn(sd, pre, src))
 
 
-def decoder_layer(sd, pre, tgt, memory, nhead, tgt_kpm, mem_kpm, pos):
+def decoder_layer(sd, pre, tgt, memory, nhead, tgt_kpm, mem_kpm, pos, drop=None):
+    if drop is not None:
+        a = mha(sd, pre + 'self_attn.', tgt, tgt, tgt, nhead, tgt_kpm, drop, pre + 'attn')
+        tgt = _ln(sd, pre + 'norm1.', tgt + drop(pre + 'res1', a))
+        a = mha(sd, pre + 'multihead_attn.', tgt, memory + pos, memory, nhead, mem_kpm, drop, pre + 'cross')
+        tgt = _ln(sd, pre + 'norm2.', tgt + drop(pre + 'res2', a))
+        return _ln(sd, pre + 'norm3.', tgt + drop(pre + 'res3', _ffn(sd, pre, tgt, drop)))
     tgt = _ln(sd, pre + 'norm1.', tgt + mha(sd, pre + 'self_attn.', tgt, tgt, tgt, nhead, tgt_kpm))
     tgt = _ln(sd, pre + 'norm2.', tgt + mha(sd, pre + 'multihead_attn.', tgt, memory + pos, memory, nhead, mem_kpm))
     return _ln(sd, pre + 'norm3.', tgt + _ffn(sd, pre, tgt))
@@ -90,10 +108,10 @@ def transformer(sd, src, mask, pos_embed, tgt, tgt_key_padding_mask, nhead, pre=
     return y.transpose(0, 1), memory.permute(1, 2, 0).reshape(bs, c, h, w)
 
 
-def torch_encoder(sd, pre, x, nhead, key_padding_mask):
+def torch_encoder(sd, pre, x, nhead, key_padding_mask, drop=None):
     """nn.TransformerEncoder of post-norm nn.TransformerEncoderLayer(relu); x seq-first [L, B, E]."""
     for i in range(_count_layers(sd, pre + 'layers.')):
-        x = encoder_layer(sd, pre + f'layers.{i}.', x, nhead, key_padding_mask, None)
+        x = encoder_layer(sd, pre + f'layers.{i}.', x, nhead, key_padding_mask, None, drop)
     return x
 
 
