@@ -36,6 +36,7 @@
  *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
  *   ldetr_lsap_f64                scipy.optimize.linear_sum_assignment as used at metrics/metric_layoutnet.py:111,125,240
  *   ldetr_layoutnet_features_f32  LayoutNet.extract_features, the feature network of the layout FID: training/networks_layoutnet.py:48-66
+ *   ldetr_layoutnet_forward_f32   LayoutNet.forward in eval mode (validation of the detector's training): training/networks_layoutnet.py:68-86
  *   ldetr_feature_stats_f64       FeatureStats.append with capture_mean_cov: metrics/metric_utils_layout.py:97-112
  *   ldetr_box_giou_pairwise_f32   box_cxcywh_to_xyxy + box_iou + generalized_box_iou: detr_util/box_ops.py:19-71
  *   ldetr_bmm_strided_f32         torch.bmm inside nn.MultiheadAttention when the regulariser phases differentiate it twice:
@@ -485,6 +486,22 @@ int ldetr_lsap_f64(const double* cost, int batch, int n, int maximize, int* row_
  *   linear2.weight, linear2.bias, norm2.weight, norm2.bias. */
 int ldetr_layoutnet_features_f32(const float* bbox, const int64_t* label, const uint8_t* padding_mask, const int* label_map, int map_len,
                                  const float* weights, int64_t weights_len, int num_label, int B, int N, float* out, void* stream);
+
+/* LayoutNet.forward (training/networks_layoutnet.py:68-86) in eval mode in one launch: the encoder above, its row 0 as the features,
+ * fc_out_disc, relu(dec_fc_in([features, pos_token[n]])), the four decoder layers with padding_mask as key mask (no class token),
+ * fc_out_cls and sigmoid(fc_out_bbox).  bbox / label / padding_mask as above (no label map: forward has none), N + 1 <= 16,
+ * num_label <= 16.  Outputs are DENSE: logit_disc [B], logit_cls [B][N][num_label], bbox_pred [B][N][4], features [B][256] (may be
+ * NULL); padded rows are written as 0 and the caller gathers the valid ones in batch-major order.  A valid element whose label is
+ * outside [0, num_label) turns every output of that sample into NaN, nothing is read out of bounds.  The features are bit-identical to
+ * ldetr_layoutnet_features_f32's, and a sample's outputs do not depend on the rest of the batch.
+ * enc_weights: the packed buffer of ldetr_layoutnet_features_f32 (enc_len = 256 num_label + 1453312).
+ * dec_weights: a second packed fp32 buffer of dec_len = 1473060 floats in this order (row-major, nn.Module layouts):
+ *   pos_token [50][256], dec_fc_in.weight, dec_fc_in.bias, then per dec_transformer layer 0..3 the twelve tensors in the encoder's
+ *   order, fc_out_cls.weight zero-padded to [16][256], fc_out_cls.bias to [16], fc_out_bbox.weight to [16][256], fc_out_bbox.bias
+ *   to [16], fc_out_disc.weight [256], fc_out_disc.bias padded to [4]. */
+int ldetr_layoutnet_forward_f32(const float* bbox, const int64_t* label, const uint8_t* padding_mask, const float* enc_weights,
+                                int64_t enc_len, const float* dec_weights, int64_t dec_len, int num_label, int B, int N,
+                                float* logit_disc, float* logit_cls, float* bbox_pred, float* features, void* stream);
 
 /* FeatureStats.append with capture_mean_cov (metrics/metric_utils_layout.py:97-112) on resident accumulators: x [n][F] fp32;
  * raw_mean [F] += sum_i x_i and raw_cov [F][F] += sum_i x_i x_i^T, every product and sum in float64.  F a multiple of 16, 16 <= F <= 256.

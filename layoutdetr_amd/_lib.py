@@ -122,6 +122,7 @@ SIGNATURES = {
     'ldetr_ema_lerp_f32': [_P, _P, _L, _F, _P],
     'ldetr_lsap_f64': [_P, _I, _I, _I, _P, _P, _P],
     'ldetr_layoutnet_features_f32': [_P, _P, _P, POINTER(c_int), _I, _P, _L, _I, _I, _I, _P, _P],
+    'ldetr_layoutnet_forward_f32': [_P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     'ldetr_feature_stats_f64': [_P, _L, _I, _P, _P, _P],
     'ldetr_box_giou_pairwise_f32': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, c_double, _P],
     'ldetr_bmm_strided_f32': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],

@@ -5,14 +5,22 @@ These are tiny [B, 9, 9] tensor programs (device-side glue around the hot kernel
 import torch
 
 
+DETECTOR_13_LABEL_NAMES = ('rico', 'enrico', 'clay', 'ads_banner_collection', 'AMT_uploaded_ads_banners', 'cgl_dataset')
+
+
+def detector_num_label(pth):
+    """The label count of the detector file `pth` (reference :28): 13 when its path contains one of the dataset names the reference lists, else 5.
+    The metric (LayoutFID) and the detector's trainer (train_layoutnet.py) both take it from here."""
+    return 13 if any(n in pth for n in DETECTOR_13_LABEL_NAMES) else 5
+
+
 class LayoutFID(object):
     """The feature detector of the layout FID (reference :26-35): LayoutNet with 13 labels for the dataset names the reference lists, else 5,
     its weights from a reference `layoutnet_<dataset>.pth.tar` (strict: anything else is refused), in eval mode on `device`."""
 
     def __init__(self, pth, device):
         from ..training.networks_layoutnet import LayoutNet
-        num_label = 13 if any(n in pth for n in ('rico', 'enrico', 'clay', 'ads_banner_collection', 'AMT_uploaded_ads_banners', 'cgl_dataset')) else 5
-        self.model = LayoutNet(num_label).to(device)
+        self.model = LayoutNet(detector_num_label(pth)).to(device)
         state_dict = torch.load(pth, map_location=device)
         self.model.load_state_dict(state_dict, strict=True)
         self.model.requires_grad_(False)

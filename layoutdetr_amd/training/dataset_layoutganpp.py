@@ -310,6 +310,14 @@ class LayoutDataset(Dataset):
         return dict(name=meta['attr']['name'], W_page=meta['attr']['width'], H_page=meta['attr']['height'],
                     bboxes=bboxes_batch.astype(np.float32), labels=labels_batch.astype(np.int64), texts=texts_batch, mask=mask), int(mask.sum())
 
+    def layouts(self):
+        """The layouts of all items without their images: bboxes [n, 9, 4] float32, labels [n, 9] int64, mask [n, 9] bool (True = a real
+        element) as torch tensors, in item order (max_size honoured).  Reads non_image.json's fields only; no PNG is decoded."""
+        fields = [self._fields(int(i))[0] for i in self._raw_idx]
+        return (torch.from_numpy(np.stack([f['bboxes'] for f in fields]).astype(np.float32)),
+                torch.from_numpy(np.stack([f['labels'] for f in fields]).astype(np.int64)),
+                torch.from_numpy(np.stack([f['mask'] for f in fields]).astype(np.bool_)))
+
     def _load_raw_data(self, raw_idx):
         raw_idx = int(raw_idx)
         out, n = self._fields(raw_idx)
