@@ -34,6 +34,8 @@
  *                                 generate.py:267-269, 280-282
  *   ldetr_resample_coeffs_filter, ldetr_layout_raster_cell_size, ldetr_layout_raster_u8
  *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
+ *   ldetr_patch_resize_u8, ldetr_image_raster_u8
+ *                                 the `images` snapshot grids: util.py:144-325 (convert_layout_to_real_image[_with_background], skimage resize)
  *   ldetr_lsap_f64                scipy.optimize.linear_sum_assignment as used at metrics/metric_layoutnet.py:111,125,240
  *   ldetr_layoutnet_features_f32  LayoutNet.extract_features, the feature network of the layout FID: training/networks_layoutnet.py:48-66
  *   ldetr_layoutnet_forward_f32   LayoutNet.forward in eval mode (validation of the detector's training): training/networks_layoutnet.py:68-86
@@ -468,6 +470,55 @@ typedef struct ldetr_layout_raster_args {
 int ldetr_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t* bounds, int32_t* weights, int64_t weights_capacity, int* ksize_out);
 int ldetr_layout_raster_cell_size(int W, int H, int S, int* wn_out, int* hn_out);
 int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* stream);
+
+/* The `images` / `images_with_background` snapshot grids (util.py:144-231 convert_layout_to_real_image, save_real_image; :234-325 the
+ * _with_background pair), two launches per grid (csrc/patch_resize.hip, csrc/layout_raster.hip; DESIGN.md section 13, rules 8-12).
+ * ldetr_patch_resize_u8: every job resizes one uint8 [h][w][3] image of source buffer 0 or 1 to [h'][w'][3] in `dst` as
+ * skimage.transform.resize(anti_aliasing=True) does (util.py:171, 240, 262): Gaussian with the mirror boundary, then linear interpolation, in fp32
+ * from host-built tables.  An axis table in the pool is, in 32-bit words: [radius r][2r + 1 Gaussian weights, fp32 bits][i0 x out][i1 x out]
+ * [w0 x out, fp32 bits][w1 x out, fp32 bits], i0 / i1 the mirror-mapped source indices of output o and w0 / w1 their weights.  The entry validates on
+ * the host before launch: job offsets against the three buffer sizes, table offsets and lengths against tables_len, every i0 / i1 against the source
+ * axis (read from tables_host, the host copy of the pool).  Limits: 1 <= size <= 16384 per axis, r <= 4096, and the source window of ONE output pixel
+ * (about (2 + 2 r_y) x (2 + 2 r_x) pixels) must fit the kernel's LDS buffers (10240 + 5120 floats): an error otherwise.  n_jobs == 0 returns 0.
+ * ldetr_image_raster_u8: cell b pastes, in stable descending order of w * h of bbox[b] (fp32), the resized patch of every valid slot at its paste
+ * rectangle rects[b][i] = (x1, y1, x2, y2), x2 / y2 exclusive, the patch being [y2 - y1][x2 - x1][3] at patch_off[b][i] of `pixels`, over the resized
+ * background at page_off[b] (W x H of page_wh[b]) or a white page (-1); then the resize, letterbox and grid tail of ldetr_layout_raster_u8.  A slot
+ * whose rectangle is empty or wholly off the page, or whose area is NaN, draws nothing.  Validated on the host: N <= 16, S, page sizes, coefficient
+ * tables, patch and background extents against pixels_bytes. */
+typedef struct ldetr_patch_resize_args {
+    int struct_bytes;             /* sizeof(ldetr_patch_resize_args) as the caller sees it */
+    int n_jobs;
+    const uint8_t* src0;          /* device: source buffer 0 (element crops) */
+    int64_t src0_bytes;
+    const uint8_t* src1;          /* device: source buffer 1 (page backgrounds), NULL when unused */
+    int64_t src1_bytes;
+    uint8_t* dst;                 /* device */
+    int64_t dst_bytes;
+    const int64_t* jobs;          /* HOST [n_jobs][9] = (source buffer, src byte offset, h, w, dst byte offset, h', w', axis-0 table offset, axis-1 table offset) */
+    const int32_t* tables;        /* device pool of axis tables */
+    const int32_t* tables_host;   /* HOST: the same words */
+    int64_t tables_len;
+    int32_t* jobs_dev;            /* device scratch, n_jobs * 16 int32 */
+} ldetr_patch_resize_args;
+typedef struct ldetr_image_raster_args {
+    int struct_bytes;             /* sizeof(ldetr_image_raster_args) as the caller sees it */
+    int B, N, S, nrow;
+    const float* bbox;            /* device [B][N][4] (xc, yc, w, h): the generated boxes, read for the draw order */
+    const uint8_t* valid;         /* HOST [B][N], non-zero = paste the slot */
+    const int32_t* rects;         /* HOST [B][N][4] */
+    const int64_t* patch_off;     /* HOST [B][N] */
+    const int64_t* page_off;      /* HOST [B], -1 = white page */
+    const int32_t* page_wh;       /* HOST [B][2] */
+    const uint8_t* pixels;        /* device: the resized patches and backgrounds (ldetr_patch_resize_u8's dst) */
+    int64_t pixels_bytes;
+    const int32_t* coeffs;        /* as ldetr_layout_raster_args */
+    int64_t coeffs_len;
+    const int64_t* cell_coeffs;
+    int32_t* cells_dev;           /* device scratch, B * 128 int32 */
+    uint8_t* out;                 /* device [Hg][Wg][3] */
+} ldetr_image_raster_args;
+int ldetr_patch_resize_u8(const ldetr_patch_resize_args* a, void* stream);
+int ldetr_image_raster_u8(const ldetr_image_raster_args* a, void* stream);
 
 /* Batched linear-sum-assignment (Hungarian / shortest augmenting path) on device.
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;

@@ -86,6 +86,21 @@ class LayoutRasterArgs(Structure):
                 ('coeffs', c_void_p), ('coeffs_len', c_int64), ('cell_coeffs', c_void_p), ('cells_dev', c_void_p), ('out', c_void_p)]
 
 
+class PatchResizeArgs(Structure):
+    """ldetr_patch_resize_args."""
+    _fields_ = [('struct_bytes', c_int), ('n_jobs', c_int), ('src0', c_void_p), ('src0_bytes', c_int64), ('src1', c_void_p), ('src1_bytes', c_int64),
+                ('dst', c_void_p), ('dst_bytes', c_int64), ('jobs', c_void_p), ('tables', c_void_p), ('tables_host', c_void_p), ('tables_len', c_int64),
+                ('jobs_dev', c_void_p)]
+
+
+class ImageRasterArgs(Structure):
+    """ldetr_image_raster_args."""
+    _fields_ = [('struct_bytes', c_int), ('B', c_int), ('N', c_int), ('S', c_int), ('nrow', c_int),
+                ('bbox', c_void_p), ('valid', c_void_p), ('rects', c_void_p), ('patch_off', c_void_p), ('page_off', c_void_p), ('page_wh', c_void_p),
+                ('pixels', c_void_p), ('pixels_bytes', c_int64), ('coeffs', c_void_p), ('coeffs_len', c_int64), ('cell_coeffs', c_void_p),
+                ('cells_dev', c_void_p), ('out', c_void_p)]
+
+
 _P = c_void_p
 _I = c_int
 _L = c_int64
@@ -159,6 +174,8 @@ SIGNATURES = {
     'ldetr_resample_coeffs_filter': [_I, _I, _I, _P, _P, _L, _P],
     'ldetr_layout_raster_cell_size': [_I, _I, _I, _P, _P],
     'ldetr_layout_raster_u8': [_P, _P],
+    'ldetr_patch_resize_u8': [_P, _P],
+    'ldetr_image_raster_u8': [_P, _P],
     'ldetr_p3_split_f32': [_P, _L, _P, _L, _I, _P],
     'ldetr_p3_merge_f32': [_P, _P, _L, _L, _I, _P],
     'ldetr_p3_weight_bwd': [_P, _P, _P, _I, _I, _I, _I, _P],

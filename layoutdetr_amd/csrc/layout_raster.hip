@@ -2,6 +2,7 @@
 //     convert_layout_to_image: boxes sorted by area, one ImageDraw.rectangle(outline, fill with alpha 100) each on a page-sized canvas   util.py:85-103
 //     PIL resize to the canvas size (BILINEAR), expand2square                                                                            util.py:105-112, 71-82
 //     ToTensor, torch.stack, torchvision make_grid(padding=2) + save_image                                                               util.py:123-141
+// (and, as ldetr_image_raster_u8, the compositing half of save_real_image / save_real_image_with_background, util.py:144-325: see the kernel's comment)
 // as ONE launch per grid: every cell, the letterbox bars and the grid padding are written here (no memset before the launch), and the
 // page-resolution image never exists in HBM.  Integer arithmetic end to end, so the grid is bit-identical to the reference's PNG pixels.
 //
@@ -36,6 +37,7 @@ namespace ldetr {
 constexpr int LR_THREADS = 256;
 constexpr int LR_MAX_N = 16;
 constexpr int LR_CELL_INTS = 32;          // per-cell descriptor, see the host entry
+constexpr int LR_IMAGE_CELL_INTS = 128;   // the image kinds' descriptor: the same head, then (x1, y1, x2, y2, offset low, offset high) per slot from int 32
 constexpr int LR_HBUF_BYTES = 44 * 1024;  // horizontal-pass rows of a band
 constexpr int LR_SRC_BYTES = 16 * 1024;   // source rows in flight
 constexpr int LR_MAX_BAND = 32;
@@ -60,7 +62,11 @@ __device__ __forceinline__ unsigned lr_blend(unsigned c, unsigned d) {
     return ((t >> 8) + t) >> 8;
 }
 
-// grid (bands, xmaps * ymaps)
+// grid (bands, xmaps * ymaps).  IMAGE (ldetr_image_raster_u8, util.py:144-325): the page is not drawn with rectangles but pasted with resized text
+// patches -- per source pixel the LAST element in draw order whose clipped paste rectangle [x1, x2) x [y1, y2) covers it gives the pixel, read from
+// its resized patch in `pages` (here the output buffer of ldetr_patch_resize_u8); otherwise the resized background or white.  The sort, the two
+// 8-bit passes, the letterbox and the grid tail are the same code.
+template <bool IMAGE>
 __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterParams p) {
     __shared__ unsigned char hbuf[LR_HBUF_BYTES];
     __shared__ unsigned char sbuf[LR_SRC_BYTES];
@@ -68,10 +74,12 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
     __shared__ unsigned bcol[LR_MAX_N];
     __shared__ float barea[LR_MAX_N];
     __shared__ int bok[LR_MAX_N];
+    __shared__ long boff[IMAGE ? LR_MAX_N : 1];
+    constexpr int CI = IMAGE ? LR_IMAGE_CELL_INTS : LR_CELL_INTS;
     const int slot = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
     const int S = p.S, P = p.pad;
     const bool live = slot < p.B;                                   // the last grid row may have empty slots: written as zeros
-    const int* cell = p.cells + (long)(live ? slot : 0) * LR_CELL_INTS;
+    const int* cell = p.cells + (long)(live ? slot : 0) * CI;
     const int R = live ? cell[13] : S;
     if (band * R >= S) return;
     const int cy = slot / p.xmaps, cx = slot % p.xmaps;
@@ -90,12 +98,18 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
                 const float* b = p.bbox + ((long)slot * p.N + tid) * 4;
                 const float xc = b[0], yc = b[1], w = b[2], h = b[3];
                 a = w * h;
-                const float fx1 = (xc - w / 2.f) * (float)W, fx2 = (xc + w / 2.f) * (float)W;
-                const float fy1 = (yc - h / 2.f) * (float)H, fy2 = (yc + h / 2.f) * (float)H;
-                ok = !(a != a || fx1 != fx1 || fx2 != fx2 || fy1 != fy1 || fy2 != fy2);
-                X1 = lr_trunc(fx1); X2 = lr_trunc(fx2); Y1 = lr_trunc(fy1); Y2 = lr_trunc(fy2);
-                if (X1 > X2) { const int t = X1; X1 = X2; X2 = t; }
-                if (Y1 > Y2) { const int t = Y1; Y1 = Y2; Y2 = t; }
+                if constexpr (IMAGE) {
+                    const int* e = cell + 32 + 6 * tid;
+                    ok = !(a != a);
+                    X1 = e[0]; Y1 = e[1]; X2 = e[2]; Y2 = e[3];
+                } else {
+                    const float fx1 = (xc - w / 2.f) * (float)W, fx2 = (xc + w / 2.f) * (float)W;
+                    const float fy1 = (yc - h / 2.f) * (float)H, fy2 = (yc + h / 2.f) * (float)H;
+                    ok = !(a != a || fx1 != fx1 || fx2 != fx2 || fy1 != fy1 || fy2 != fy2);
+                    X1 = lr_trunc(fx1); X2 = lr_trunc(fx2); Y1 = lr_trunc(fy1); Y2 = lr_trunc(fy2);
+                    if (X1 > X2) { const int t = X1; X1 = X2; X2 = t; }
+                    if (Y1 > Y2) { const int t = Y1; Y1 = Y2; Y2 = t; }
+                }
             }
             bok[tid] = ok; barea[tid] = a;
         }
@@ -105,7 +119,8 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
                 int rank = 0;
                 for (int j = 0; j < LR_MAX_N; j++) rank += (bok[j] && (barea[j] > a || (barea[j] == a && j < tid))) ? 1 : 0;
                 bx[rank][0] = X1; bx[rank][1] = Y1; bx[rank][2] = X2; bx[rank][3] = Y2;
-                bcol[rank] = (unsigned)cell[16 + tid];
+                if constexpr (IMAGE) boff[rank] = (long)cell[32 + 6 * tid + 5] * 4294967296L + (long)(unsigned)cell[32 + 6 * tid + 4];
+                else bcol[rank] = (unsigned)cell[16 + tid];
             }
         }
         __syncthreads();
@@ -130,12 +145,22 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
                     const unsigned char* px = p.pages + page_off + ((long)y * W + x) * 3;
                     d0 = px[0]; d1 = px[1]; d2 = px[2];
                 }
-                for (int k = 0; k < nb; k++) {
-                    const int bX1 = bx[k][0], bY1 = bx[k][1], bX2 = bx[k][2], bY2 = bx[k][3];
-                    if (x < bX1 || x > bX2 || y < bY1 || y > bY2) continue;
-                    const unsigned c = bcol[k], c0 = c & 255u, c1 = (c >> 8) & 255u, c2 = (c >> 16) & 255u;
-                    if (x == bX1 || x == bX2 || y == bY1 || y == bY2) { d0 = c0; d1 = c1; d2 = c2; }
-                    else { d0 = lr_blend(c0, d0); d1 = lr_blend(c1, d1); d2 = lr_blend(c2, d2); }
+                if constexpr (IMAGE) {
+                    for (int k = nb - 1; k >= 0; k--) {
+                        const int bX1 = bx[k][0], bY1 = bx[k][1], bX2 = bx[k][2], bY2 = bx[k][3];
+                        if (x < bX1 || x >= bX2 || y < bY1 || y >= bY2) continue;
+                        const unsigned char* px = p.pages + boff[k] + ((long)(y - bY1) * (bX2 - bX1) + (x - bX1)) * 3;
+                        d0 = px[0]; d1 = px[1]; d2 = px[2];
+                        break;
+                    }
+                } else {
+                    for (int k = 0; k < nb; k++) {
+                        const int bX1 = bx[k][0], bY1 = bx[k][1], bX2 = bx[k][2], bY2 = bx[k][3];
+                        if (x < bX1 || x > bX2 || y < bY1 || y > bY2) continue;
+                        const unsigned c = bcol[k], c0 = c & 255u, c1 = (c >> 8) & 255u, c2 = (c >> 16) & 255u;
+                        if (x == bX1 || x == bX2 || y == bY1 || y == bY2) { d0 = c0; d1 = c1; d2 = c2; }
+                        else { d0 = lr_blend(c0, d0); d1 = lr_blend(c1, d1); d2 = lr_blend(c2, d2); }
+                    }
                 }
                 unsigned char* o = dst + i * 3;
                 o[0] = (unsigned char)d0; o[1] = (unsigned char)d1; o[2] = (unsigned char)d2;
@@ -248,6 +273,47 @@ extern "C" int ldetr_layout_raster_cell_size(int W, int H, int S, int* wn_out, i
     return LDETR_OK;
 }
 
+// make_grid's layout (rule 7) for B cells of S x S
+static int lr_grid_dims(const char* who, int B, int nrow_arg, int S, int* xmaps, int* ymaps, int* pad, long* Hg, long* Wg) {
+    *xmaps = 1; *ymaps = 1; *pad = 0;
+    if (B > 1) {
+        int nrow = nrow_arg > 0 ? nrow_arg : (int)ceil(sqrt((double)B));
+        *xmaps = nrow < B ? nrow : B; *ymaps = (B + *xmaps - 1) / *xmaps; *pad = 2;
+    }
+    *Hg = (long)*ymaps * (S + *pad) + *pad; *Wg = (long)*xmaps * (S + *pad) + *pad;
+    LDETR_CHECK(*Hg * *Wg * 3 < (1L << 31) && (long)*xmaps * *ymaps <= 65535, "%s: grid too large (%ld x %ld)", who, *Hg, *Wg);
+    return LDETR_OK;
+}
+
+// the part of a cell's descriptor both entries share: resized size, letterbox offsets, coefficient tables, band height (c[0..5], c[8..11], c[13])
+static int lr_cell_geometry(const char* who, int b, int W, int H, int S, const int64_t* cc, int64_t coeffs_len, int32_t* c, int* bands) {
+    LDETR_CHECK(W >= 1 && H >= 1 && W < (1 << 24) && H < (1 << 24), "%s: cell %d: bad page size %d x %d", who, b, W, H);
+    int Wn, Hn;
+    ldetr_layout_raster_cell_size(W, H, S, &Wn, &Hn);
+    LDETR_CHECK(Wn >= 1 && Hn >= 1, "%s: cell %d: page %d x %d leaves no pixel at canvas size %d", who, b, W, H, S);
+    LDETR_CHECK((long)W * 3 <= LR_SRC_BYTES, "%s: cell %d: page wider than %d pixels", who, b, LR_SRC_BYTES / 3);
+    const bool hskip = W == Wn, vskip = H == Hn;
+    LDETR_CHECK(hskip ? cc[0] < 0 : (cc[0] >= 0 && cc[1] >= 1 && cc[0] + (2 + cc[1]) * Wn <= coeffs_len),
+                "%s: cell %d: horizontal coefficient table outside the pool (or given for a skipped pass)", who, b);
+    LDETR_CHECK(vskip ? cc[2] < 0 : (cc[2] >= 0 && cc[3] >= 1 && cc[2] + (2 + cc[3]) * Hn <= coeffs_len),
+                "%s: cell %d: vertical coefficient table outside the pool (or given for a skipped pass)", who, b);
+    // band height: the intermediate rows of a band must fit LR_HBUF_BYTES
+    const long cap = LR_HBUF_BYTES / ((long)Wn * 3);
+    const double scale = (double)H / Hn, support = scale < 1.0 ? 1.0 : scale;
+    int R = LR_MAX_BAND;
+    auto rows = [&](int r) { return vskip ? (long)r : (long)ceil(r * scale + 2.0 * support) + 2; };
+    while (R > 1 && rows(R) > cap) R--;
+    LDETR_CHECK(rows(R) <= cap, "%s: cell %d: page %d x %d too tall for one band of the canvas", who, b, W, H);
+    c[0] = W; c[1] = H; c[2] = Wn; c[3] = Hn;
+    c[4] = W > H ? 0 : (S - Wn) / 2; c[5] = W > H ? (S - Hn) / 2 : 0;
+    c[8] = hskip ? -1 : (int32_t)cc[0]; c[9] = hskip ? 0 : (int32_t)cc[1];
+    c[10] = vskip ? -1 : (int32_t)cc[2]; c[11] = vskip ? 0 : (int32_t)cc[3];
+    c[13] = R;
+    const int nb = (S + R - 1) / R;
+    if (nb > *bands) *bands = nb;
+    return LDETR_OK;
+}
+
 extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* stream) {
     LDETR_CHECK(a, "layout_raster: null argument block");
     LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_layout_raster_args), "layout_raster: argument block of %d bytes, this library expects %d", a->struct_bytes,
@@ -261,24 +327,16 @@ extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* s
                 "layout_raster: null pointer");
     LDETR_CHECK(a->n_colors >= 1, "layout_raster: empty palette");
     LDETR_CHECK(a->n_pages >= 0 && (a->n_pages == 0 || (a->pages && a->page_table && a->page_index)), "layout_raster: pages given without buffer, table or index");
-    int xmaps = 1, ymaps = 1, pad = 0;
-    if (B > 1) {
-        int nrow = a->nrow > 0 ? a->nrow : (int)ceil(sqrt((double)B));
-        xmaps = nrow < B ? nrow : B; ymaps = (B + xmaps - 1) / xmaps; pad = 2;
-    }
-    const long Hg = (long)ymaps * (S + pad) + pad, Wg = (long)xmaps * (S + pad) + pad;
-    LDETR_CHECK(Hg * Wg * 3 < (1L << 31) && (long)xmaps * ymaps <= 65535, "layout_raster: grid too large (%ld x %ld)", Hg, Wg);
+    int xmaps, ymaps, pad;
+    long Hg, Wg;
+    if (int rc = lr_grid_dims("layout_raster", B, a->nrow, S, &xmaps, &ymaps, &pad, &Hg, &Wg)) return rc;
     static thread_local std::vector<int32_t> cells;                    // outlives the call: the upload below reads it
     cells.assign((size_t)B * LR_CELL_INTS, 0);
     int bands = 1;
     for (int b = 0; b < B; b++) {
         int32_t* c = cells.data() + (size_t)b * LR_CELL_INTS;
         const int W = a->page_wh[2 * b], H = a->page_wh[2 * b + 1];
-        LDETR_CHECK(W >= 1 && H >= 1 && W < (1 << 24) && H < (1 << 24), "layout_raster: cell %d: bad page size %d x %d", b, W, H);
-        int Wn, Hn;
-        ldetr_layout_raster_cell_size(W, H, S, &Wn, &Hn);
-        LDETR_CHECK(Wn >= 1 && Hn >= 1, "layout_raster: cell %d: page %d x %d leaves no pixel at canvas size %d", b, W, H, S);
-        LDETR_CHECK((long)W * 3 <= LR_SRC_BYTES, "layout_raster: cell %d: page wider than %d pixels", b, LR_SRC_BYTES / 3);
+        if (int rc = lr_cell_geometry("layout_raster", b, W, H, S, a->cell_coeffs + 4 * (long)b, a->coeffs_len, c, &bands)) return rc;
         long off = -1;
         const int pi = a->n_pages > 0 ? a->page_index[b] : -1;
         LDETR_CHECK(pi >= -1 && pi < a->n_pages, "layout_raster: cell %d: page index %d outside the page table (%d pages)", b, pi, a->n_pages);
@@ -288,19 +346,6 @@ extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* s
             LDETR_CHECK(t[0] >= 0 && t[0] + (int64_t)W * H * 3 <= a->pages_bytes, "layout_raster: cell %d: page %d reaches past the page buffer", b, pi);
             off = t[0];
         }
-        const int64_t* cc = a->cell_coeffs + 4 * (long)b;                 // (h offset, h ksize, v offset, v ksize)
-        const bool hskip = W == Wn, vskip = H == Hn;
-        LDETR_CHECK(hskip ? cc[0] < 0 : (cc[0] >= 0 && cc[1] >= 1 && cc[0] + (2 + cc[1]) * Wn <= a->coeffs_len),
-                    "layout_raster: cell %d: horizontal coefficient table outside the pool (or given for a skipped pass)", b);
-        LDETR_CHECK(vskip ? cc[2] < 0 : (cc[2] >= 0 && cc[3] >= 1 && cc[2] + (2 + cc[3]) * Hn <= a->coeffs_len),
-                    "layout_raster: cell %d: vertical coefficient table outside the pool (or given for a skipped pass)", b);
-        // band height: the intermediate rows of a band must fit LR_HBUF_BYTES
-        const long cap = LR_HBUF_BYTES / ((long)Wn * 3);
-        const double scale = (double)H / Hn, support = scale < 1.0 ? 1.0 : scale;
-        int R = LR_MAX_BAND;
-        auto rows = [&](int r) { return vskip ? (long)r : (long)ceil(r * scale + 2.0 * support) + 2; };
-        while (R > 1 && rows(R) > cap) R--;
-        LDETR_CHECK(rows(R) <= cap, "layout_raster: cell %d: page %d x %d too tall for one band of the canvas", b, W, H);
         unsigned mask = 0;
         for (int i = 0; i < N; i++) {
             if (!a->valid[(long)b * N + i]) continue;
@@ -309,14 +354,8 @@ extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* s
             mask |= 1u << i;
             c[16 + i] = a->palette[3 * lab] | (a->palette[3 * lab + 1] << 8) | (a->palette[3 * lab + 2] << 16);
         }
-        c[0] = W; c[1] = H; c[2] = Wn; c[3] = Hn;
-        c[4] = W > H ? 0 : (S - Wn) / 2; c[5] = W > H ? (S - Hn) / 2 : 0;
         c[6] = (int32_t)(off & 0xffffffffL); c[7] = (int32_t)(off >> 32);
-        c[8] = hskip ? -1 : (int32_t)cc[0]; c[9] = hskip ? 0 : (int32_t)cc[1];
-        c[10] = vskip ? -1 : (int32_t)cc[2]; c[11] = vskip ? 0 : (int32_t)cc[3];
-        c[12] = (int32_t)mask; c[13] = R;
-        const int nb = (S + R - 1) / R;
-        if (nb > bands) bands = nb;
+        c[12] = (int32_t)mask;
     }
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemcpyAsync(a->cells_dev, cells.data(), cells.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
@@ -324,6 +363,56 @@ extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* s
     LayoutRasterParams p; memset(&p, 0, sizeof(p));
     p.bbox = a->bbox; p.pages = a->pages; p.coeffs = a->coeffs; p.cells = a->cells_dev; p.out = a->out;
     p.B = B; p.N = N; p.S = S; p.xmaps = xmaps; p.ymaps = ymaps; p.pad = pad; p.Hg = (int)Hg; p.Wg = (int)Wg;
-    hipLaunchKernelGGL(layout_raster_kernel, dim3((unsigned)bands, (unsigned)(xmaps * ymaps)), LR_THREADS, 0, st, p);
+    hipLaunchKernelGGL(layout_raster_kernel<false>, dim3((unsigned)bands, (unsigned)(xmaps * ymaps)), LR_THREADS, 0, st, p);
     return check_launch("layout_raster");
+}
+
+extern "C" int ldetr_image_raster_u8(const ldetr_image_raster_args* a, void* stream) {
+    LDETR_CHECK(a, "image_raster: null argument block");
+    LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_image_raster_args), "image_raster: argument block of %d bytes, this library expects %d", a->struct_bytes,
+                (int)sizeof(ldetr_image_raster_args));
+    const int B = a->B, N = a->N, S = a->S;
+    LDETR_CHECK(B >= 0, "image_raster: negative B (got %d)", B);
+    LDETR_CHECK(N >= 1 && N <= LR_MAX_N, "image_raster: needs 1 <= N <= 16 elements per layout (got %d)", N);
+    LDETR_CHECK(S >= 2 && S % 2 == 0 && S <= 4096, "image_raster: the canvas size must be even and in [2, 4096] (got %d)", S);
+    if (B == 0) return LDETR_OK;
+    LDETR_CHECK(a->bbox && a->valid && a->rects && a->patch_off && a->page_off && a->page_wh && a->cell_coeffs && a->coeffs && a->cells_dev && a->out,
+                "image_raster: null pointer");
+    LDETR_CHECK(a->pixels_bytes >= 0 && (a->pixels || a->pixels_bytes == 0), "image_raster: pixel buffer size without buffer");
+    int xmaps, ymaps, pad;
+    long Hg, Wg;
+    if (int rc = lr_grid_dims("image_raster", B, a->nrow, S, &xmaps, &ymaps, &pad, &Hg, &Wg)) return rc;
+    static thread_local std::vector<int32_t> cells;
+    cells.assign((size_t)B * LR_IMAGE_CELL_INTS, 0);
+    int bands = 1;
+    for (int b = 0; b < B; b++) {
+        int32_t* c = cells.data() + (size_t)b * LR_IMAGE_CELL_INTS;
+        const int W = a->page_wh[2 * b], H = a->page_wh[2 * b + 1];
+        if (int rc = lr_cell_geometry("image_raster", b, W, H, S, a->cell_coeffs + 4 * (long)b, a->coeffs_len, c, &bands)) return rc;
+        const int64_t off = a->page_off[b];
+        LDETR_CHECK(off >= -1 && (off < 0 || off + (int64_t)W * H * 3 <= a->pixels_bytes), "image_raster: cell %d: resized background reaches past the pixel buffer", b);
+        unsigned mask = 0;
+        for (int i = 0; i < N; i++) {
+            if (!a->valid[(long)b * N + i]) continue;
+            const int32_t* r = a->rects + ((long)b * N + i) * 4;           // the UNCLIPPED paste rectangle: the patch is (y2 - y1) x (x2 - x1)
+            if (r[2] <= r[0] || r[3] <= r[1] || r[2] <= 0 || r[3] <= 0 || r[0] >= W || r[1] >= H) continue;      // draws nothing
+            const int64_t po = a->patch_off[(long)b * N + i];
+            LDETR_CHECK(po >= 0 && po + ((int64_t)r[3] - r[1]) * ((int64_t)r[2] - r[0]) * 3 <= a->pixels_bytes,
+                        "image_raster: cell %d: the resized patch of slot %d reaches past the pixel buffer", b, i);
+            mask |= 1u << i;
+            int32_t* e = c + 32 + 6 * i;
+            e[0] = r[0]; e[1] = r[1]; e[2] = r[2]; e[3] = r[3];             // (the kernel only visits page pixels: that is the clip)
+            e[4] = (int32_t)(po & 0xffffffffL); e[5] = (int32_t)(po >> 32);
+        }
+        c[6] = (int32_t)(off & 0xffffffffL); c[7] = (int32_t)(off >> 32);
+        c[12] = (int32_t)mask;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(a->cells_dev, cells.data(), cells.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { set_error("image_raster: descriptor upload: %s", hipGetErrorString(e)); return LDETR_ERR_LAUNCH; }
+    LayoutRasterParams p; memset(&p, 0, sizeof(p));
+    p.bbox = a->bbox; p.pages = a->pixels; p.coeffs = a->coeffs; p.cells = a->cells_dev; p.out = a->out;
+    p.B = B; p.N = N; p.S = S; p.xmaps = xmaps; p.ymaps = ymaps; p.pad = pad; p.Hg = (int)Hg; p.Wg = (int)Wg;
+    hipLaunchKernelGGL(layout_raster_kernel<true>, dim3((unsigned)bands, (unsigned)(xmaps * ymaps)), LR_THREADS, 0, st, p);
+    return check_launch("image_raster");
 }

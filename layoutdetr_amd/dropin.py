@@ -166,9 +166,15 @@ def install_plugins():
 
 
 def main(argv):
-    if not argv:
-        raise SystemExit('usage: python -m layoutdetr_amd.dropin <script.py> [script args...]')
     import os
+    argv = list(argv)
+    while argv and argv[0].startswith('--image-snapshot-kinds'):      # before the script: which snapshot kinds training_loop writes (training/snapshot_images.py)
+        opt = argv.pop(0)
+        value = opt.split('=', 1)[1] if '=' in opt else (argv.pop(0) if argv else '')
+        from .training.snapshot_images import KINDS_ENV, parse_kinds
+        os.environ[KINDS_ENV] = ','.join(parse_kinds(value))
+    if not argv:
+        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] <script.py> [script args...]')
     sys.path.insert(0, os.path.dirname(os.path.abspath(argv[0])))
     for pkg in ('training', 'torch_utils', 'torch_utils.ops'):     # import the reference's packages first so aliases attach to them
         try:

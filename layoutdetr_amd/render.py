@@ -176,3 +176,252 @@ def save_png(grid, path):
     if grid.dtype != torch.uint8 or grid.ndim != 3 or grid.shape[2] != 3:
         raise ValueError('save_png: expected a uint8 [H, W, 3] grid')
     PIL.Image.fromarray(grid.detach().cpu().numpy(), 'RGB').save(path)
+
+
+# ---- the `images` kinds: text patches pasted at the generated boxes (util.py:144-325; DESIGN.md §13 rules 8-12) ----
+
+IMAGE_CANVAS = 1024          # save_real_image's default size_canvas
+MAX_RESIZE = 16384           # csrc/patch_resize.hip: largest source / target axis
+
+_axis_cache = {}    # (in, out) -> int32 words of one axis table
+
+
+def resize_axis_table(n_in, n_out):
+    """One axis of skimage.transform.resize(anti_aliasing=True) as the kernel reads it (rule 10), int32 words: [r][2r + 1 Gaussian weights][i0][i1][w0][w1],
+    built in double, the weights stored as fp32 bits."""
+    key = (int(n_in), int(n_out))
+    hit = _axis_cache.get(key)
+    if hit is not None:
+        return hit
+    n_in, n_out = key
+    f = n_in / n_out
+    sigma = max(0.0, (f - 1.0) / 2.0)
+    r = int(4.0 * sigma + 0.5) if sigma > 0 else 0
+    if r > 0:
+        k = np.arange(-r, r + 1, dtype=np.float64)
+        g = np.exp(-0.5 * (k / sigma) ** 2)
+        g = g / g.sum()
+    else:
+        g = np.ones(1, np.float64)
+    c = (np.arange(n_out, dtype=np.float64) + 0.5) * f - 0.5
+    i0 = np.floor(c)
+    t = c - i0
+
+    def mirror(i):
+        if n_in == 1:
+            return np.zeros_like(i, dtype=np.int64)
+        p = 2 * (n_in - 1)
+        m = np.mod(i.astype(np.int64), p)
+        return np.where(m >= n_in, p - m, m)
+    words = np.concatenate([np.asarray([r], np.int32), g.astype(np.float32).view(np.int32), mirror(i0).astype(np.int32), mirror(i0 + 1).astype(np.int32),
+                            (1.0 - t).astype(np.float32).view(np.int32), t.astype(np.float32).view(np.int32)])
+    if len(_axis_cache) > 4096:
+        _axis_cache.clear()
+    _axis_cache[key] = words
+    return words
+
+
+class PatchSet(object):
+    """The uint8 crops of a grid's elements (LayoutDataset.patch_crops: rule 8) in ONE device buffer + the table [cells, N, 3] = (byte offset, w, h)
+    the resize jobs are read through; offset -1: the element has no drawable crop.  `crops`: per cell a list of N entries, uint8 [h, w, 3] arrays
+    (numpy or torch, host or device) or None."""
+
+    def __init__(self, crops, device):
+        crops = [list(c) for c in crops]
+        n = max([len(c) for c in crops] + [1])
+        table = np.full((len(crops), n, 3), -1, np.int64)
+        parts, at = [], 0
+        for b, cell in enumerate(crops):
+            for i, c in enumerate(cell):
+                if c is None:
+                    continue
+                c = torch.as_tensor(c)
+                if c.dtype != torch.uint8 or c.ndim != 3 or c.shape[2] != 3 or c.shape[0] < 1 or c.shape[1] < 1:
+                    raise ValueError('PatchSet: every crop must be a non-empty uint8 [h, w, 3]')
+                table[b, i] = (at, int(c.shape[1]), int(c.shape[0]))
+                parts.append(c.contiguous().reshape(-1))
+                at += c.numel()
+        self.table = table
+        if parts and all(p.device.type == 'cpu' for p in parts):
+            self.buffer = torch.cat(parts).to(device)                 # one upload
+        else:
+            self.buffer = torch.cat([p.to(device) for p in parts]) if parts else torch.zeros(1, dtype=torch.uint8, device=device)
+        core.require_gpu(self.buffer)
+
+    def __len__(self):
+        return self.table.shape[0]
+
+
+def paste_rects(bbox_fake, page_wh):
+    """Rule 9 on host arrays: int64 [B, N, 4] = (x1, y1, x2, y2), the fp32 corners (xc -+ w / 2) * W, (yc -+ h / 2) * H rounded half to even
+    (util.py:167-169); a NaN corner gives an empty rectangle."""
+    b = np.asarray(bbox_fake, np.float32)
+    wh = np.asarray(page_wh, np.float32).reshape(-1, 1, 2)
+    two = np.float32(2)
+    with np.errstate(all='ignore'):
+        xc, yc, w, h = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+        c = np.stack([(xc - w / two) * wh[..., 0], (yc - h / two) * wh[..., 1], (xc + w / two) * wh[..., 0], (yc + h / two) * wh[..., 1]], -1)
+        assert c.dtype == np.float32
+        bad = np.isnan(c).any(-1)
+        r = np.clip(np.rint(np.nan_to_num(c, nan=0.0)).astype(np.float64), -2 ** 30, 2 ** 30).astype(np.int64)
+    r[bad] = 0
+    return r
+
+
+class _ResizeJobs(object):
+    """The job list of ONE ldetr_patch_resize_u8 launch: rows (source buffer, src offset, h, w, dst offset, h', w', axis tables) + the pool of the
+    axis tables they name."""
+
+    def __init__(self):
+        self.jobs, self.axis_at, self.pool, self.pool_len, self.dst_bytes = [], {}, [], 0, 0
+
+    def _table(self, n_in, n_out):
+        key = (n_in, n_out)
+        if key not in self.axis_at:
+            words = resize_axis_table(n_in, n_out)
+            self.axis_at[key] = self.pool_len
+            self.pool.append(words)
+            self.pool_len += words.size
+        return self.axis_at[key]
+
+    def add(self, buf, off, h, w, ho, wo):
+        """-> the byte offset of the [ho, wo, 3] result in the output buffer."""
+        if min(h, w, ho, wo) < 1 or max(h, w, ho, wo) > MAX_RESIZE:
+            raise ValueError(f'patch resize: {w} x {h} -> {wo} x {ho}: every axis must be in [1, {MAX_RESIZE}]')
+        at = self.dst_bytes
+        self.jobs.append((buf, off, h, w, at, ho, wo, self._table(h, ho), self._table(w, wo)))
+        self.dst_bytes += ho * wo * 3
+        return at
+
+    def launch(self, src0, src1, dev):
+        """uint8 device buffer of dst_bytes bytes (at least 1), written by one launch."""
+        pixels = torch.empty(max(self.dst_bytes, 1), dtype=torch.uint8, device=dev)
+        if not self.jobs:
+            return pixels
+        jobs_h = np.ascontiguousarray(np.asarray(self.jobs, np.int64).reshape(-1, 9))
+        tables_h = np.ascontiguousarray(np.concatenate(self.pool))
+        tables_d = torch.from_numpy(tables_h).to(dev)
+        jobs_d = torch.empty(len(self.jobs) * 16, dtype=torch.int32, device=dev)
+        a = _lib.PatchResizeArgs()
+        a.struct_bytes, a.n_jobs = ctypes.sizeof(_lib.PatchResizeArgs), len(self.jobs)
+        a.src0, a.src0_bytes = src0.data_ptr(), src0.numel()
+        if src1 is not None:
+            a.src1, a.src1_bytes = src1.data_ptr(), src1.numel()
+        a.dst, a.dst_bytes = pixels.data_ptr(), pixels.numel()
+        a.jobs, a.tables, a.tables_host, a.tables_len, a.jobs_dev = jobs_h.ctypes.data, tables_d.data_ptr(), tables_h.ctypes.data, tables_h.size, jobs_d.data_ptr()
+        core.check(core.lib().ldetr_patch_resize_u8(ctypes.byref(a), core.stream()), 'patch_resize')
+        return pixels
+
+
+def resize_u8(images, sizes):
+    """skimage.transform.resize(im, (h', w'), anti_aliasing=True) of every uint8 [h, w, 3] device tensor of `images` to its (h', w') of `sizes`, by rule 10
+    of DESIGN.md §13, in ONE launch -> list of uint8 [h', w', 3] device tensors (views of one buffer)."""
+    images = list(images)
+    core.require_gpu(*images)
+    if not images:
+        return []
+    pages = PageSet(images)
+    rj = _ResizeJobs()
+    at = [rj.add(0, int(off), int(h), int(w), int(ho), int(wo)) for (off, w, h), (ho, wo) in zip(pages.table.tolist(), sizes)]
+    pixels = rj.launch(pages.buffer, None, images[0].device)
+    return [pixels[o:o + int(ho) * int(wo) * 3].view(int(ho), int(wo), 3) for o, (ho, wo) in zip(at, sizes)]
+
+
+def image_grid(bbox_fake, bbox_real, valid, patches, page_wh, backgrounds=None, canvas=IMAGE_CANVAS, nrow=None, patch_index=None, background_index=None):
+    """uint8 [Hg, Wg, 3] device tensor: the pixels the reference's save_real_image (backgrounds=None, util.py:207-231) or
+    save_real_image_with_background (util.py:298-325) grid holds, by the rule of DESIGN.md §13 (rules 8-12), in two launches: one batched
+    anti-aliased resize of every element crop (and page background) to its paste size, one compositing raster.
+
+    bbox_fake [B, N, 4] fp32 in GPU memory (ONE device-to-host copy of it gives the paste rectangles); bbox_real [B, N, 4]: the boxes the crops were
+    made from, read on the host only to check the crop sizes (pass a CPU tensor to avoid a second small copy); valid [B, N] (host);
+    patches: a PatchSet of the crops LayoutDataset.patch_crops made from bbox_real; page_wh: (W, H) or [B, 2]; backgrounds: a PageSet (or uint8
+    [h, w, 3] device tensors) of any size, resized to the page.  patch_index / background_index [B]: the PatchSet cell / page each grid cell
+    uses (default b -> b; several cells may share one).  There is no CPU fallback."""
+    core.require_gpu(bbox_fake)
+    if bbox_fake.ndim != 3 or bbox_fake.shape[-1] != 4 or bbox_real.shape != bbox_fake.shape:
+        raise ValueError('image_grid: bbox_fake and bbox_real must both be [B, N, 4]')
+    if not isinstance(patches, PatchSet):
+        raise ValueError('image_grid: patches must be a render.PatchSet')
+    B, N = int(bbox_fake.shape[0]), int(bbox_fake.shape[1])
+    S = int(canvas)
+    if N < 1 or N > MAX_BOXES:
+        raise ValueError(f'image_grid: 1 <= N <= {MAX_BOXES} elements per layout (got {N})')
+    if S < 2 or S % 2 != 0:
+        raise ValueError(f'image_grid: the canvas size must be even (got {canvas})')
+    if nrow is not None and int(nrow) < 1:
+        raise ValueError('image_grid: nrow must be positive')
+    dev = bbox_fake.device
+    if B == 0:
+        return torch.zeros((0, 0, 3), dtype=torch.uint8, device=dev)
+    core.require_gpu(patches.buffer)
+    valid_h = _host(valid, np.uint8).reshape(B, N).copy()
+    wh = _host(page_wh, np.int32)
+    wh = np.ascontiguousarray(np.broadcast_to(wh.reshape(1, 2), (B, 2))) if wh.size == 2 else wh.reshape(B, 2)
+    if (wh < 1).any():
+        raise ValueError('image_grid: bad page size')
+    pidx = np.arange(B) if patch_index is None else _host(patch_index, np.int64).reshape(-1)
+    if pidx.size != B or (pidx < 0).any() or (pidx >= len(patches)).any() or patches.table.shape[1] < N:
+        raise ValueError('image_grid: patch_index must name one PatchSet cell of at least N slots per grid cell')
+    rects = paste_rects(core.f32c(bbox_fake).cpu().numpy(), wh)                              # the one device-to-host copy of the generated boxes
+    boxes_real = _host(bbox_real, np.float32)
+    # rule 8's crop size, to catch a PatchSet that was not made from these real boxes
+    with np.errstate(all='ignore'):
+        real_wh = np.nan_to_num(boxes_real[..., 2:4] * wh.astype(np.float32).reshape(B, 1, 2), nan=-1.0, posinf=-1.0, neginf=-1.0).astype(np.int64)
+    bg_table = None
+    if backgrounds is not None:
+        if not isinstance(backgrounds, PageSet):
+            backgrounds = PageSet(backgrounds)
+        core.require_gpu(backgrounds.buffer)
+        bidx = np.arange(B) if background_index is None else _host(background_index, np.int64).reshape(-1)
+        if bidx.size != B or (bidx < 0).any() or (bidx >= len(backgrounds)).any():
+            raise ValueError('image_grid: background_index must name one page per cell')
+        bg_table = backgrounds.table[bidx]
+    rj, bg_done = _ResizeJobs(), {}
+    job = rj.add
+    patch_off = np.full((B, N), -1, np.int64)
+    page_off = np.full(B, -1, np.int64)
+    for b in range(B):
+        W, H = int(wh[b, 0]), int(wh[b, 1])
+        if bg_table is not None:
+            off, bw, bh = (int(v) for v in bg_table[b])
+            if (off, W, H) not in bg_done:                            # cells that share a background and a page size share its resize
+                bg_done[(off, W, H)] = job(1, off, bh, bw, H, W)
+            page_off[b] = bg_done[(off, W, H)]
+        for i in range(N):
+            off, cw, ch = (int(v) for v in patches.table[pidx[b], i])
+            x1, y1, x2, y2 = (int(v) for v in rects[b, i])
+            if not valid_h[b, i] or off < 0 or x2 <= x1 or y2 <= y1 or x2 <= 0 or y2 <= 0 or x1 >= W or y1 >= H:
+                valid_h[b, i] = 0                                     # draws nothing (rules 8, 9)
+                continue
+            if (cw, ch) != (int(real_wh[b, i, 0]), int(real_wh[b, i, 1])):
+                raise ValueError(f'image_grid: cell {b} slot {i}: the crop is {cw} x {ch}, bbox_real asks for {int(real_wh[b, i, 0])} x {int(real_wh[b, i, 1])}')
+            patch_off[b, i] = job(0, off, ch, cw, y2 - y1, x2 - x1)
+    pairs, cell_pairs = [], []
+    for W, H in wh.tolist():
+        Wn, Hn = cell_size(W, H, S)
+        if Wn < 1 or Hn < 1:
+            raise ValueError(f'image_grid: a {W} x {H} page leaves no pixel at canvas size {S}')
+        hp, vp = ((W, Wn) if W != Wn else None), ((H, Hn) if H != Hn else None)
+        cell_pairs.append((hp, vp))
+        for pr in (hp, vp):
+            if pr is not None and pr not in pairs:
+                pairs.append(pr)
+    cpool, where = _coeff_pool(sorted(pairs), dev)
+    cc = np.asarray([[where[hp][0] if hp else -1, where[hp][1] if hp else 0, where[vp][0] if vp else -1, where[vp][1] if vp else 0]
+                     for hp, vp in cell_pairs], np.int64)
+    lib, st = core.lib(), core.stream()
+    pixels = rj.launch(patches.buffer, None if backgrounds is None else backgrounds.buffer, dev)
+    Hg, Wg, _, _ = grid_shape(B, S, nrow)
+    rects32 = np.ascontiguousarray(np.clip(rects, -2 ** 30, 2 ** 30).astype(np.int32))
+    bb = core.f32c(bbox_fake)
+    cells = torch.empty(B * 128, dtype=torch.int32, device=dev)
+    out = torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=dev)
+    a = _lib.ImageRasterArgs()
+    a.struct_bytes = ctypes.sizeof(_lib.ImageRasterArgs)
+    a.B, a.N, a.S, a.nrow = B, N, S, 0 if nrow is None else int(nrow)
+    a.bbox, a.valid, a.rects, a.patch_off, a.page_off, a.page_wh = bb.data_ptr(), valid_h.ctypes.data, rects32.ctypes.data, patch_off.ctypes.data, page_off.ctypes.data, wh.ctypes.data
+    a.pixels, a.pixels_bytes = pixels.data_ptr(), pixels.numel()
+    a.coeffs, a.coeffs_len, a.cell_coeffs = cpool.data_ptr(), cpool.numel(), cc.ctypes.data
+    a.cells_dev, a.out = cells.data_ptr(), out.data_ptr()
+    core.check(lib.ldetr_image_raster_u8(ctypes.byref(a), st), 'image_raster')
+    return out

@@ -13,7 +13,8 @@ nine slots with a validity mask (`to_dense_batch`, :29-41).
   `background_size` + ImageNet normalisation + HWC -> CHW run on the GPU for the whole batch (`background_to_tensor`, two
   launches, bit-identical to Pillow's Lanczos and the reference's fp32 lines :330-338).  The 9 x 3 patch PNGs per sample
   (:283-327) are NEVER opened: `networks_detr` reads `bbox_patch` for its shape only (networks_detr.py:133-187), so 'patches' is
-  a 0-stride zero view of the right shape; 'patches_orig' / 'patch_masks' / 'background_orig' (snapshot image grids only) are absent.
+  a 0-stride zero view of the right shape; 'patches_orig' / 'patch_masks' / 'background_orig' (snapshot image grids only) are absent:
+  the `images` snapshot kinds read their uint8 crops through `patch_crops(idx)` instead.
   `LayoutDataset.collate` keeps the pages uint8 and the patch placeholder 0-stride (torch's default collate would materialise 7 MB
   of zeros per sample); `training_loop()` passes it to the DataLoader and calls `batch_backgrounds_to_device`.
 * mode='reference': every key of the reference's item, computed on the host exactly as the reference does (PIL decode + Lanczos
@@ -317,6 +318,33 @@ class LayoutDataset(Dataset):
         return (torch.from_numpy(np.stack([f['bboxes'] for f in fields]).astype(np.float32)),
                 torch.from_numpy(np.stack([f['labels'] for f in fields]).astype(np.int64)),
                 torch.from_numpy(np.stack([f['mask'] for f in fields]).astype(np.bool_)))
+
+    def patch_crops(self, idx):
+        """The uint8 text patches of item `idx` as the `images` snapshot kinds paste them (util.py:159-163; DESIGN.md §13 rule 8): per slot the
+        centre width x height window of '<base>_<k>_patch_orig.png', width = int(bbox[2] * W_page), height = int(bbox[3] * H_page) (fp32 products,
+        truncated), or None for a padding slot and for a window that is empty or leaves the canvas (the reference would wrap or fail).  Works in
+        either mode; only this item's patch files are decoded, and `__getitem__` is untouched."""
+        raw_idx = int(self._raw_idx[idx])
+        fields, n = self._fields(raw_idx)
+        base = self._samples[raw_idx][0]
+        W, H = np.float32(fields['W_page']), np.float32(fields['H_page'])
+        out = [None] * len(fields['mask'])
+        for k in range(n):
+            b = fields['bboxes'][k].astype(np.float32)
+            with np.errstate(all='ignore'):
+                fw, fh = b[2] * W, b[3] * H
+            if not (np.isfinite(fw) and np.isfinite(fh)):
+                continue
+            width, height = int(fw), int(fh)
+            po = np.array(self._decode(base + '_%d_patch_orig.png' % k))
+            if po.ndim != 3 or po.shape[2] != 3:
+                raise ValueError(f'{base}_{k}_patch_orig.png: expected an RGB patch (:305-315)')
+            cy, cx = po.shape[0] // 2, po.shape[1] // 2
+            y0, y1, x0, x1 = cy - height // 2, cy + height - height // 2, cx - width // 2, cx + width - width // 2
+            if width < 1 or height < 1 or y0 < 0 or x0 < 0 or y1 > po.shape[0] or x1 > po.shape[1]:
+                continue
+            out[k] = np.ascontiguousarray(po[y0:y1, x0:x1])
+        return out
 
     def _load_raw_data(self, raw_idx):
         raw_idx = int(raw_idx)

@@ -4,7 +4,12 @@
 Written per set (`train`, and `val` when a validation set is configured):
     <set>_layouts_real.png, <set>_layouts_fake_<kimg>.png                      the reference's save_image grids (canvas 128), bit-identical pixels
     <set>_layouts_over_background_real.png, ..._fake_<kimg>.png                this package's own kind: the same boxes over the sample's decoded page, canvas 256
-The reference's `*_images_*` kinds paste the decoded text patches (skimage.transform.resize); this path never decodes patches, so they are not built.
+and, when asked for (`kinds`; training_loop reads LDETR_IMAGE_SNAPSHOT_KINDS, `python -m layoutdetr_amd.dropin --image-snapshot-kinds=...` sets it):
+    <set>_images_real.png, <set>_images_fake_<kimg>.png                        util.save_real_image (:144-231): every element's text patch resized to its box
+    <set>_images_with_background_real.png, ..._fake_<kimg>.png                 util.save_real_image_with_background (:234-325): the same over the page
+both at canvas 1024 by render.image_grid (two launches per grid; the rule is DESIGN.md §13, rules 8-12).  The patches are LayoutDataset.patch_crops of the
+grid items, read once at setup; the page under `images_with_background` is the decoded page (the reference resizes its 256 x 256 training background up).
+A dataset without patch files skips these two kinds with one printed note.
 
 The grid items are read from a dataset instance of their own, opened here and closed afterwards: the training set's archive handle is shared
 with the DataLoader's forked workers, and a read through it in the main process would move a file offset they use.  `z` comes from a private
@@ -19,6 +24,23 @@ from .. import render
 
 LAYOUT_CANVAS = 128          # util.save_image's default size_canvas
 BACKGROUND_CANVAS = 256
+IMAGE_CANVAS = render.IMAGE_CANVAS   # util.save_real_image's default size_canvas
+KINDS = ('layouts', 'layouts_over_background', 'images', 'images_with_background')
+DEFAULT_KINDS = KINDS[:2]
+KINDS_ENV = 'LDETR_IMAGE_SNAPSHOT_KINDS'
+
+
+def parse_kinds(kinds):
+    """A tuple of kinds from a tuple / list or a comma-separated string; None or '' -> DEFAULT_KINDS.  An unknown kind is an error."""
+    if kinds is None or kinds == '':
+        return DEFAULT_KINDS
+    if isinstance(kinds, str):
+        kinds = [k.strip() for k in kinds.split(',') if k.strip()]
+    kinds = tuple(kinds)
+    bad = [k for k in kinds if k not in KINDS]
+    if bad:
+        raise ValueError(f'unknown image snapshot kind(s) {bad}: choose from {list(KINDS)}')
+    return tuple(k for k in KINDS if k in kinds)
 
 
 def grid_indices(n_items, batch_size, random_seed=0):
@@ -49,9 +71,10 @@ class SnapshotGrid(object):
     masks, resized backgrounds, conditioning labels) and the fixed z; for the whole grid the real boxes, the uint8 pages with their sizes, and
     host copies of the masks and labels (the raster entry reads those on the host)."""
 
-    def __init__(self, name, dataset, G, batch_size, batch_gpu, device, colors, random_seed=0):
+    def __init__(self, name, dataset, G, batch_size, batch_gpu, device, colors, random_seed=0, kinds=DEFAULT_KINDS, image_canvas=IMAGE_CANVAS):
         from .training_loop import assemble_batch
         self.name, self.device, self.colors = name, device, [tuple(int(v) for v in c) for c in colors]
+        self.kinds, self.image_canvas = parse_kinds(kinds), int(image_canvas)
         self.indices = grid_indices(len(dataset), batch_size, random_seed)
         items = [dataset[i] for i in self.indices]
         collate = dataset.collate if (getattr(dataset, 'mode', None) == 'device' and hasattr(dataset, 'collate')) else torch.utils.data.default_collate
@@ -61,11 +84,20 @@ class SnapshotGrid(object):
         if all(isinstance(p, np.ndarray) and p.dtype == np.uint8 and p.ndim == 3 for p in pages):
             self.pages = render.PageSet([torch.from_numpy(np.ascontiguousarray(p)).to(device) for p in pages])
             self.pages_wh = [(int(p.shape[1]), int(p.shape[0])) for p in pages]      # the decoded page's own size
+        self.patches = None
+        if 'images' in self.kinds or 'images_with_background' in self.kinds:
+            try:
+                if not hasattr(dataset, 'patch_crops'):
+                    raise KeyError('the dataset has no patch_crops')
+                self.patches = render.PatchSet([dataset.patch_crops(i) for i in self.indices], device)
+            except (KeyError, FileNotFoundError) as e:
+                print(f'Image snapshots: the `images` kinds are skipped for the {name} set: no text patches ({e})')
         self.splits = []
         for lo in range(0, len(items), batch_gpu):
             samples, real_c = collate(items[lo:lo + batch_gpu])
             self.splits.append(assemble_batch(samples, real_c, G, dataset.background_size_for_training, device))
         self.bbox_real = torch.cat([s['bbox_real'] for s in self.splits])
+        self.bbox_real_host = self.bbox_real.cpu()      # (the `images` kinds check the crop sizes against it on the host)
         self.valid = (~torch.cat([s['padding_mask'] for s in self.splits])).cpu()
         self.labels = torch.cat([s['bbox_class'] for s in self.splits]).cpu()
         gen = torch.Generator(device=device)
@@ -85,9 +117,23 @@ class SnapshotGrid(object):
 
     def grids(self, bbox):
         """{kind: uint8 grid} for one set of boxes: one raster launch per grid."""
-        out = {'layouts': render.layout_grid(bbox, self.valid, self.labels, self.colors, self.page_wh, canvas=LAYOUT_CANVAS)}
-        if self.pages is not None:
+        out = {}
+        if 'layouts' in self.kinds:
+            out['layouts'] = render.layout_grid(bbox, self.valid, self.labels, self.colors, self.page_wh, canvas=LAYOUT_CANVAS)
+        if 'layouts_over_background' in self.kinds and self.pages is not None:
             out['layouts_over_background'] = render.layout_grid(bbox, self.valid, self.labels, self.colors, self.pages_wh, pages=self.pages, canvas=BACKGROUND_CANVAS)
+        if self.patches is not None:
+            for kind, pages in (('images', None), ('images_with_background', self.pages)):
+                if kind not in self.kinds or (kind == 'images_with_background' and pages is None):
+                    continue
+                try:
+                    out[kind] = render.image_grid(bbox, self.bbox_real_host, self.valid, self.patches, self.page_wh, backgrounds=pages, canvas=self.image_canvas)
+                except RuntimeError as e:
+                    # a generated box so small that one output pixel's source window exceeds the resize kernel's LDS (DESIGN.md §13: zoom 14 on both
+                    # axes): a preview must not end a training run, so this grid is left out of this tick, with a note
+                    if 'floats of LDS' not in str(e):
+                        raise
+                    print(f'Image snapshots: {self.name}_{kind} is not written at this tick: {e}')
         return out
 
     def write(self, run_dir, bbox, tag):
@@ -98,7 +144,7 @@ class SnapshotGrid(object):
         return paths
 
 
-def _open(name, dataset_kwargs, G, batch_size, batch_gpu, device, colors, random_seed):
+def _open(name, dataset_kwargs, G, batch_size, batch_gpu, device, colors, random_seed, kinds, image_canvas):
     from .training_loop import construct_class_by_name
     dataset = construct_class_by_name(**dataset_kwargs)
     try:
@@ -106,7 +152,7 @@ def _open(name, dataset_kwargs, G, batch_size, batch_gpu, device, colors, random
         item = dataset[0][0] if len(dataset) else {}
         if colors is None or 'W_page' not in item or 'H_page' not in item:
             return None, colors
-        return SnapshotGrid(name, dataset, G, batch_size, batch_gpu, device, colors, random_seed), colors
+        return SnapshotGrid(name, dataset, G, batch_size, batch_gpu, device, colors, random_seed, kinds, image_canvas), colors
     finally:
         if hasattr(dataset, 'close'):
             dataset.close()
@@ -119,16 +165,18 @@ class ImageSnapshots(object):
         self.run_dir, self.grids = run_dir, grids
 
     @classmethod
-    def setup(cls, run_dir, training_set_kwargs, validation_set_kwargs, G, batch_size, batch_gpu, device, random_seed=0):
-        """None (after one printed note) when the dataset's items carry no page sizes or the dataset has no palette."""
+    def setup(cls, run_dir, training_set_kwargs, validation_set_kwargs, G, batch_size, batch_gpu, device, random_seed=0, kinds=None, image_canvas=IMAGE_CANVAS):
+        """None (after one printed note) when the dataset's items carry no page sizes or the dataset has no palette.  kinds: a subset of KINDS
+        (tuple or comma-separated string); None = DEFAULT_KINDS, the two `layouts` kinds."""
+        kinds = parse_kinds(kinds)
         with preserved_rng(device):
-            train, colors = _open('train', training_set_kwargs, G, batch_size, batch_gpu, device, None, random_seed)
+            train, colors = _open('train', training_set_kwargs, G, batch_size, batch_gpu, device, None, random_seed, kinds, image_canvas)
             if train is None:
                 print('Image snapshots skipped: the dataset has no page sizes (W_page / H_page) or no colors')
                 return None
             grids = [train]
             if validation_set_kwargs:
-                val, _ = _open('val', validation_set_kwargs, G, batch_size, batch_gpu, device, colors, random_seed)      # training_set.colors for both (:218)
+                val, _ = _open('val', validation_set_kwargs, G, batch_size, batch_gpu, device, colors, random_seed, kinds, image_canvas)      # training_set.colors for both (:218)
                 if val is not None:
                     grids.append(val)
             self = cls(run_dir, grids)

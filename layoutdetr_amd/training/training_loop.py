@@ -894,7 +894,9 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     samples and a private fixed z every `image_snapshot_ticks` ticks and at the end, pixels as the reference's save_image writes them, plus this package's
     `*_layouts_over_background_*` (the boxes over the decoded page), one raster launch per grid (training/snapshot_images.py, render.py); like the metrics
     they leave G_ema and the generator states as found, and a dataset without page sizes or palette is skipped with one printed note.  NOT done here (a
-    note is printed): augment pipe, ADA, the `*_images_*` snapshot kinds (they paste decoded text patches; this path never decodes patches), tensorboard.
+    note is printed): augment pipe, ADA, tensorboard.  The reference's `*_images_*` / `*_images_with_background_*` snapshot kinds (:213-216, 220-223, 379-382,
+    389-392: text patches pasted at the boxes) are opt-in, because the signature above is the reference's and takes no further keyword: the environment variable
+    LDETR_IMAGE_SNAPSHOT_KINDS names the kinds to write, comma-separated (default 'layouts,layouts_over_background'; add 'images,images_with_background').
     Returns dict(stats of the last tick, G, D, G_ema, snapshot_pkl, metrics)."""
     import json
     import os
@@ -945,11 +947,12 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     dp = DataParallelStep(world_size=num_gpus)
     ema = EmaTracker(phases[0], G_ema)
     if rank == 0:
-        print('Not run on this path: augment pipe, ADA, the *_images_* snapshot kinds (text patches are never decoded here), tensorboard')
+        print('Not run on this path: augment pipe, ADA, tensorboard')
     image_snapshots = None
     if rank == 0 and image_snapshot_ticks is not None and run_dir and os.path.isdir(run_dir):      # :148-150, :209-223
-        from .snapshot_images import ImageSnapshots
-        image_snapshots = ImageSnapshots.setup(run_dir, training_set_kwargs, validation_set_kwargs, G, batch_size, batch_gpu, device)
+        from .snapshot_images import KINDS_ENV, ImageSnapshots
+        image_snapshots = ImageSnapshots.setup(run_dir, training_set_kwargs, validation_set_kwargs, G, batch_size, batch_gpu, device,
+                                               kinds=os.environ.get(KINDS_ENV))
     if rank == 0:
         print(f'Training for {total_kimg} kimg...')
     cur_nimg, cur_tick, tick_start_nimg, tick_start = resume_kimg * 1000, 0, resume_kimg * 1000, time.time()
