@@ -18,6 +18,8 @@
  *   ldetr_act_bwd_reduce_f32      bias_act backward + dx.sum(): torch_utils/ops/bias_act.py:160-173
  *   ldetr_mul_reduce_f32          `x * styles` / `x * dcoefs` backward: training/networks_stylegan2.py:66-72
  *   ldetr_torgb_bwd_f32           ToRGBLayer backward: training/networks_stylegan2.py:349-353
+ *   ldetr_sg2_handoff_f32         the element-wise chain between two layers of SynthesisNetwork's backward (styles, toRGB, lrelu and their
+ *                                 reductions): training/networks_stylegan2.py:307-326, 349-353, 441-456
  *   ldetr_maxpool3x3s2_*_f32      torchvision ResNet stem max-pool (called via detr_backbone.py:105)
  *   ldetr_grad_sanitize_f32, ldetr_adam_step_f32, ldetr_ema_lerp_f32
  *                                 training/training_loop.py:303-313, 320-328
@@ -345,6 +347,20 @@ int ldetr_torgb_fwd_f32(const float* x, const float* w, const float* styles, con
                         int B, int64_t P, int C, void* stream);
 int ldetr_torgb_bwd_f32(const float* x, const float* dy, const float* w, const float* styles, float* dx, float* dws,
                         float* dbias, int B, int64_t P, int C, void* stream);
+/* StyleGAN2 synthesis backward, everything between two contraction launches as one streaming pass over [B][P][C] (C a multiple of 4).  x is the
+ * producer layer's saved output (after bias, lrelu and gain): the tensor the consumer conv's style gradient multiplies against, the toRGB's input
+ * and the carrier of the lrelu sign.
+ *   dv[b,p,c]         = (dxs * s_conv[b][c] + s_rgb[b][c] * sum_k dy_rgb[b,p,k] * w_rgb[k][c]) * (x > 0 ? gain : gain * alpha)
+ *   ds_conv[b][c]    += sum_p dxs * x                         dxs: the consumer conv's data gradient before its styles; optional
+ *   dws_rgb[b][k][c] += sum_p dy_rgb[b,p,k] * x               dy_rgb [B][P][3]: optional; dws_rgb goes to ldetr_torgb_bwd_finish_f32
+ *   dbias_rgb[k]     += sum_{b,p} dy_rgb[b,p,k]
+ *   dbias[c]         += sum_{b,p} dv
+ *   ddemod[b][c]     += sum_p dv * (pre(x) - bias[c]) / demod[b][c]      optional (NULL); pre(x) = x / gain or x / (gain * alpha)
+ * At least one of dxs / dy_rgb; dv may alias dxs; accumulation targets hold their starting values.  Above 32 blocks per output element the sums
+ * go through the registered workspace and a finish launch, otherwise fp32 atomics (the policy of ldetr_act_bwd_reduce_f32). */
+int ldetr_sg2_handoff_f32(const float* dxs, const float* x, const float* dy_rgb, float* dv, const float* s_conv, const float* s_rgb,
+                          const float* w_rgb, const float* bias, const float* demod, float* ds_conv, float* dws_rgb, float* dbias_rgb,
+                          float* dbias, float* ddemod, int B, int64_t P, int C, float alpha, float gain, void* stream);
 
 int ldetr_maxpool3x3s2_fwd_f32(const float* x, float* y, unsigned char* idx, int N, int H, int W, int C, void* stream);
 int ldetr_maxpool3x3s2_bwd_f32(const float* dy, const unsigned char* idx, float* dx, int N, int H, int W, int C,

@@ -3,6 +3,7 @@
 // All tensors are row-major [rows][C] with C contiguous (NHWC pixels are rows).
 #include "ldetr_common.hpp"
 #include "../../include/ldetr_hip.h"
+#include <type_traits>
 
 namespace ldetr {
 
@@ -113,51 +114,70 @@ __global__ __launch_bounds__(256) void rowreduce_kernel(RRParams p) {
 }
 
 // Second stage of the row reductions: red[b][c] += sum over the row chunks' partial sums (all samples' chunks when the
-// reduction is shared by the batch, bs == 0).  No long same-address atomic queues: with one atomic per block and channel the
-// first stage's time was (#blocks x ~0.1 us) whatever the bandwidth; here at most `segs` (<= 16) atomics meet per address.
-// grid (ceil(C / 64), B or 1, 2 * segs): z / segs = 0 -> red1, 1 -> red2; z % segs = slice of the partial rows.
+// reduction is shared by the batch, bs == 0), for up to RR_MAX_PLANES partial planes [planes][blocks][C] of one first-stage launch.
+// No long same-address atomic queues: with one atomic per block and channel the first stage's time was (#blocks x ~0.1 us)
+// whatever the bandwidth; here at most `segs` (<= 16) atomics meet per address.
+// grid (ceil(C / 64), B or 1, planes * segs): z / segs = plane; z % segs = slice of the partial rows.
 // Block = 64 channels x 4 partial-row lanes.
-__global__ __launch_bounds__(256) void rr_finish_kernel(RRParams p, int chunks, int segs) {
+enum { RR_MAX_PLANES = 6 };
+struct RRFinish {
+    float* red[RR_MAX_PLANES]; long bs[RR_MAX_PLANES];   // plane i -> red[i][b * bs[i] + c]; a NULL plane is skipped
+    const float* part; int B, C;
+};
+
+__global__ __launch_bounds__(256) void rr_finish_kernel(RRFinish f, int chunks, int segs) {
     __shared__ float sh[256];
     const int which = blockIdx.z / segs, seg = blockIdx.z % segs;
-    float* red = which ? p.red2 : p.red1;
-    const long bs = which ? p.red2_bs : p.red1_bs;
+    float* red = nullptr; long bs = 0;
+#pragma unroll
+    for (int i = 0; i < RR_MAX_PLANES; i++) if (which == i) { red = f.red[i]; bs = f.bs[i]; }
     if (!red) return;
     const bool shared_by_batch = bs == 0;
     if (shared_by_batch && blockIdx.y > 0) return;
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
-    const long nblk = (long)chunks * p.B;
-    const float* part = p.part + (which ? nblk * p.C : 0);
+    const long nblk = (long)chunks * f.B;
+    const float* part = f.part + (long)which * nblk * f.C;
     const long first = shared_by_batch ? 0 : (long)blockIdx.y * chunks, count = shared_by_batch ? nblk : chunks;
     const long per = (count + segs - 1) / segs, i0 = seg * per, i1 = min(count, i0 + per);
     float acc = 0.f;
-    if (c < p.C) {
+    if (c < f.C) {
 #pragma unroll 4
-        for (long i = i0 + lane; i < i1; i += 4) acc += part[(first + i) * p.C + c];
+        for (long i = i0 + lane; i < i1; i += 4) acc += part[(first + i) * f.C + c];
     }
     sh[threadIdx.x] = acc;
     __syncthreads();
-    if (lane == 0 && c < p.C && i0 < i1) {
+    if (lane == 0 && c < f.C && i0 < i1) {
         acc += sh[threadIdx.x + 64] + sh[threadIdx.x + 128] + sh[threadIdx.x + 192];
         float* d = red + (shared_by_batch ? 0 : (long)blockIdx.y * bs) + c;
         if (segs > 1) atomicAdd(d, acc); else *d += acc;
     }
 }
 
-static int launch_rr(RRParams& p, hipStream_t st) {
-    const int C4 = p.C / 4;
+// Row-chunk plan shared by the streaming reductions: a few blocks per CU in total, never straddling a sample.
+static dim3 rr_grid(int B, long P, int C, int* rows_pb_out) {
+    const int C4 = C / 4;
     const int TQ = C4 < 256 ? C4 : 256;
     const int RL = 256 / TQ;
-    // a few blocks per CU in total, never straddling a sample; their partial sums go through the workspace to rr_finish_kernel
     static const long target = 2048;
-    const long groups = (long)p.B * cdiv(C4, TQ);
+    const long groups = (long)B * cdiv(C4, TQ);
     long chunks = target / groups; if (chunks < 1) chunks = 1;
-    long rows_pb = (p.P + chunks - 1) / chunks;
+    long rows_pb = (P + chunks - 1) / chunks;
     const long min_rows = (long)RL * 4;
     if (rows_pb < min_rows) rows_pb = min_rows;
     rows_pb = (rows_pb + RL - 1) / RL * RL;
-    p.rows_pb = (int)rows_pb;
-    dim3 grid((unsigned)((p.P + rows_pb - 1) / rows_pb), p.B, cdiv(C4, TQ));
+    *rows_pb_out = (int)rows_pb;
+    return dim3((unsigned)((P + rows_pb - 1) / rows_pb), B, cdiv(C4, TQ));
+}
+
+static int launch_rr_finish(const RRFinish& f, int planes, int chunks, long sharers, hipStream_t st) {
+    int segs = (int)(sharers / 32); if (segs < 1) segs = 1; if (segs > 16) segs = 16;
+    hipLaunchKernelGGL(rr_finish_kernel, dim3(cdiv(f.C, 64), f.B, planes * segs), 256, 0, st, f, chunks, segs);
+    return check_launch("rowreduce_finish");
+}
+
+static int launch_rr(RRParams& p, hipStream_t st) {
+    // their partial sums go through the workspace to rr_finish_kernel
+    const dim3 grid = rr_grid(p.B, p.P, p.C, &p.rows_pb);
     const long nblk = (long)grid.x * grid.y;
     // atomics queue up per output cache line: 32 per block and line at ~5 ns each, i.e. ~0.16 us per sharing block -- cheaper than
     // the ~4.5 us of a second launch up to ~30 sharers (measured: 48 us vs 10 us at 256 sharers); beyond that the partial sums go
@@ -168,9 +188,9 @@ static int launch_rr(RRParams& p, hipStream_t st) {
     else if (p.mode == RR_ACTGRAD) hipLaunchKernelGGL(rowreduce_kernel<RR_ACTGRAD>, grid, 256, 0, st, p);
     else hipLaunchKernelGGL(rowreduce_kernel<RR_MULRED>, grid, 256, 0, st, p);
     int rc = check_launch("rowreduce"); if (rc || !p.part) return rc;
-    int segs = (int)(sharers / 32); if (segs < 1) segs = 1; if (segs > 16) segs = 16;
-    hipLaunchKernelGGL(rr_finish_kernel, dim3(cdiv(p.C, 64), p.B, (p.red2 ? 2 : 1) * segs), 256, 0, st, p, (int)grid.x, segs);
-    return check_launch("rowreduce_finish");
+    RRFinish f; memset(&f, 0, sizeof(f));
+    f.red[0] = p.red1; f.bs[0] = p.red1_bs; f.red[1] = p.red2; f.bs[1] = p.red2_bs; f.part = p.part; f.B = p.B; f.C = p.C;
+    return launch_rr_finish(f, p.red2 ? 2 : 1, (int)grid.x, sharers, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -333,6 +353,200 @@ __global__ __launch_bounds__(256) void torgb_finish_kernel(const float* __restri
         const float* d = dws + (long)b * 3 * C + c;
         ds[i] = d[0] * w[c] + d[C] * w[C + c] + d[2 * C] * w[2 * C + c];
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// StyleGAN2 synthesis backward, the hand-off between two contraction launches (training/networks_stylegan2.py:307-326, :349-353): the
+// producer layer's saved output x is at once the tensor the consumer conv's style gradient multiplies against, the toRGB's input and the
+// carrier of the lrelu sign, so  dxs -> * s_conv -> (+ toRGB's dx) -> * gain * lrelu'(x)  is ONE pass over two tensors:
+//   dv[b,p,c]       = (dxs * s_conv[b][c] + s_rgb[b][c] * sum_k dy[b,p,k] * w_rgb[k][c]) * (x > 0 ? gain : gain * alpha)
+//   ds_conv[b][c]  += sum_p dxs * x                      (CONV)
+//   dws[b][k][c]   += sum_p dy[b,p,k] * x                (RGB; finished by torgb_finish_kernel)
+//   dbias_rgb[k]   += sum_{b,p} dy[b,p,k]                (RGB)
+//   dbias[c]       += sum_{b,p} dv
+//   ddemod[b][c]   += sum_p dv * (pre(x) - bias[c]) / demod[b][c]        (the formula of RR_ACTGRAD; only when ddemod != NULL)
+// toRGB's dx (three FMAs per element from a 3-channel gradient) and the styled dx never exist in memory.  Thread layout and trip shape of
+// rowreduce_kernel; partial planes in the order ds_conv, dws[0..2], dbias, ddemod (those present).
+struct HandoffParams {
+    const float* dxs; const float* x; const float* dy; float* dv;
+    const float* s_conv; const float* s_rgb; const float* w_rgb; const float* bias; const float* demod;
+    float* ds_conv; float* dws; float* dbias_rgb; float* dbias; float* ddemod;
+    float* part;         // [planes][blocks][C] partial sums instead of atomics (finished by rr_finish_kernel), or NULL
+    long P; int B, C, rows_pb;
+    float gp, gn;        // slope for x > 0 and for x <= 0, activation gain included
+};
+
+static __device__ __forceinline__ void f4_fma(float4& acc, float s, const float4& v) {
+    acc.x += s * v.x; acc.y += s * v.y; acc.z += s * v.z; acc.w += s * v.w;
+}
+static __device__ __forceinline__ void f4_add(float4& acc, const float4& v) { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
+
+template <bool CONV, bool RGB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CONV && RGB ? 4 : 5))) void sg2_handoff_kernel(HandoffParams p) {
+    __shared__ float4 sh[3][256];
+    __shared__ float4 shw[3][256];      // s_rgb[b][c] * w_rgb[k][c] of the block's channel quads: read per row, 12 registers less held per lane
+    const int C4 = p.C >> 2;
+    const int TQ = C4 < 256 ? C4 : 256;
+    const int RL = 256 / TQ;
+    const int tx = threadIdx.x % TQ, ty = threadIdx.x / TQ;
+    const int cq = blockIdx.z * TQ + tx;
+    const int b = blockIdx.y;
+    const bool active = (ty < RL) && (cq < C4);
+    const bool dd = p.ddemod != nullptr;
+    if (RGB) {
+        if (active && ty == 0) {
+            const int c = cq << 2;
+            const float4 sr = *reinterpret_cast<const float4*>(p.s_rgb + (long)b * p.C + c);
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const float4 w = *reinterpret_cast<const float4*>(p.w_rgb + (long)k * p.C + c);
+                shw[k][tx] = make_float4(sr.x * w.x, sr.y * w.y, sr.z * w.z, sr.w * w.w);
+            }
+        }
+        __syncthreads();
+    }
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 rs = zero, rb = zero, rd = zero, a0 = zero, a1 = zero, a2 = zero;
+    float db0 = 0.f, db1 = 0.f, db2 = 0.f;
+    if (active) {
+        const int c = cq << 2;
+        float4 sc = zero;
+        if (CONV) sc = *reinterpret_cast<const float4*>(p.s_conv + (long)b * p.C + c);
+        const float gp = p.gp, gn = p.gn;
+        const float ip = 1.f / gp, in = (gn != 0.f) ? 1.f / gn : 0.f;
+        // the block's rows [r0, r0 + nrows) of sample b: one 64-bit base per tensor (uniform) + an unsigned 32-bit byte offset per lane (the
+        // host checks that a chunk of rows_pb x C floats stays below 2^32 bytes): no 64-bit address arithmetic in registers
+        const long r0 = (long)blockIdx.x * p.rows_pb;
+        const int nrows = (int)(min(p.P, r0 + p.rows_pb) - r0);
+        const long base = ((long)b * p.P + r0) * p.C;
+        const char* xb = reinterpret_cast<const char*>(p.x + base);
+        const char* ab = CONV ? reinterpret_cast<const char*>(p.dxs + base) : nullptr;
+        const char* yb = RGB ? reinterpret_cast<const char*>(p.dy + ((long)b * p.P + r0) * 3) : nullptr;
+        char* ob = reinterpret_cast<char*>(p.dv + base);
+        const unsigned rowb = (unsigned)p.C * 4u, cb = (unsigned)c * 4u;
+        // four rows per trip, all loads issued before the first store (dv may alias dxs); full trips carry no bounds test at all, the chunk's
+        // last rows (fewer than 4 x RL) go one per trip
+        auto trip = [&](int r, auto un) {
+            constexpr int UN = decltype(un)::value;
+            float4 av[UN], xv[UN];
+            float d0[UN], d1[UN], d2[UN];
+#pragma unroll
+            for (int u = 0; u < UN; u++) {
+                // row r + u * RL: the u * RL rows go into the (uniform) base, so the four rows share one offset register per tensor
+                const unsigned off = (unsigned)r * rowb + cb, yo = (unsigned)r * 12u;
+                const size_t ub = (size_t)(u * RL) * rowb, uy = (size_t)(u * RL) * 12u;
+                if (CONV) av[u] = *reinterpret_cast<const float4*>(ab + ub + off);
+                xv[u] = *reinterpret_cast<const float4*>(xb + ub + off);
+                if (RGB) {
+                    d0[u] = *reinterpret_cast<const float*>(yb + uy + yo); d1[u] = *reinterpret_cast<const float*>(yb + uy + 4 + yo);
+                    d2[u] = *reinterpret_cast<const float*>(yb + uy + 8 + yo);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UN; u++) {
+                // rows are consumed one after the other: left to itself the scheduler interleaves the four rows (and their twelve LDS reads
+                // each) for ILP this HBM-bound loop has no use for, at 30 registers and one wave per SIMD
+                __builtin_amdgcn_sched_barrier(0);
+                const float4& x = xv[u];
+                float4 g = zero;
+                if (RGB) {
+                    // (the index passes through an empty asm so that the three reads stay here and are not hoisted back into registers)
+                    int wi = tx;
+                    asm volatile("" : "+v"(wi));
+                    f4_fma(g, d0[u], shw[0][wi]); f4_fma(g, d1[u], shw[1][wi]); f4_fma(g, d2[u], shw[2][wi]);
+                    f4_fma(a0, d0[u], x); f4_fma(a1, d1[u], x); f4_fma(a2, d2[u], x);
+                    db0 += d0[u]; db1 += d1[u]; db2 += d2[u];        // (every lane sums them; the first channel quad's are used)
+                }
+                if (CONV) {
+                    const float4& a = av[u];
+                    g.x += a.x * sc.x; g.y += a.y * sc.y; g.z += a.z * sc.z; g.w += a.w * sc.w;
+                    rs.x += a.x * x.x; rs.y += a.y * x.y; rs.z += a.z * x.z; rs.w += a.w * x.w;
+                }
+                float4 dv;
+                // (both products, then the choice: the slopes stay scalar operands instead of four registers held for the selects)
+                dv.x = x.x > 0.f ? g.x * gp : g.x * gn; dv.y = x.y > 0.f ? g.y * gp : g.y * gn;
+                dv.z = x.z > 0.f ? g.z * gp : g.z * gn; dv.w = x.w > 0.f ? g.w * gp : g.w * gn;
+                *reinterpret_cast<float4*>(ob + (size_t)(u * RL) * rowb + ((unsigned)r * rowb + cb)) = dv;
+                f4_add(rb, dv);
+                // pre-activation v = x / gain (x > 0) or x / (gain * alpha); u * d = v - bias.  rd sums dv * v here; "- bias * sum dv" and the
+                // division by d follow once per block below (sum dv is rb).  Summed whether or not ddemod is wanted: a few VALU operations
+                // under the loads, no branch in the loop.
+                rd.x += dv.x * (x.x > 0.f ? x.x * ip : x.x * in); rd.y += dv.y * (x.y > 0.f ? x.y * ip : x.y * in);
+                rd.z += dv.z * (x.z > 0.f ? x.z * ip : x.z * in); rd.w += dv.w * (x.w > 0.f ? x.w * ip : x.w * in);
+            }
+        };
+        int r = ty;
+#pragma nounroll
+        for (; r + 3 * RL < nrows; r += 4 * RL) trip(r, std::integral_constant<int, 4>());
+#pragma nounroll
+        for (; r < nrows; r += RL) trip(r, std::integral_constant<int, 1>());
+    }
+    const bool lead = active && ty == 0;
+    const int c = cq << 2;
+    const long nblk = (long)gridDim.x * gridDim.y, blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    // one plane's block sum -> its partial plane, or atomics into red[b * bs + c]
+    auto emit = [&](const float4& v, int plane, float* red, long bs) {
+        if (p.part) { *reinterpret_cast<float4*>(p.part + ((long)plane * nblk + blk) * p.C + c) = v; return; }
+        float* d = red + (long)b * bs + c;
+        atomicAdd(d, v.x); atomicAdd(d + 1, v.y); atomicAdd(d + 2, v.z); atomicAdd(d + 3, v.w);
+    };
+    // the row lanes' sums meet through LDS, three planes at a time
+    if (RGB) {
+        sh[0][threadIdx.x] = a0; sh[1][threadIdx.x] = a1; sh[2][threadIdx.x] = a2;
+        __syncthreads();
+        if (lead) {
+            for (int j = 1; j < RL; j++) { f4_add(a0, sh[0][j * TQ + tx]); f4_add(a1, sh[1][j * TQ + tx]); f4_add(a2, sh[2][j * TQ + tx]); }
+            const int pl = CONV ? 1 : 0;
+            emit(a0, pl, p.dws, 3L * p.C); emit(a1, pl + 1, p.dws + p.C, 3L * p.C); emit(a2, pl + 2, p.dws + 2 * p.C, 3L * p.C);
+        }
+        __syncthreads();
+    }
+    sh[0][threadIdx.x] = rs; sh[1][threadIdx.x] = rb; sh[2][threadIdx.x] = rd;
+    __syncthreads();
+    if (lead) {
+        for (int j = 1; j < RL; j++) { f4_add(rs, sh[0][j * TQ + tx]); f4_add(rb, sh[1][j * TQ + tx]); f4_add(rd, sh[2][j * TQ + tx]); }
+        const int pl = (CONV ? 1 : 0) + (RGB ? 3 : 0);
+        if (CONV) emit(rs, 0, p.ds_conv, p.C);
+        emit(rb, pl, p.dbias, 0);
+        if (dd) {
+            const float4 dmv = *reinterpret_cast<const float4*>(p.demod + (long)b * p.C + c);
+            const float4 cv = p.bias ? *reinterpret_cast<const float4*>(p.bias + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            rd.x = (rd.x - cv.x * rb.x) / dmv.x; rd.y = (rd.y - cv.y * rb.y) / dmv.y;
+            rd.z = (rd.z - cv.z * rb.z) / dmv.z; rd.w = (rd.w - cv.w * rb.w) / dmv.w;
+            emit(rd, pl + 1, p.ddemod, p.C);
+        }
+    }
+    // toRGB's bias gradient: the block's row lanes are summed through LDS first, one block issues 3 atomics (see torgb_bwd_kernel)
+    if (RGB && blockIdx.z == 0) {
+        __syncthreads();
+        float* f = reinterpret_cast<float*>(&sh[0][0]);
+        if (tx == 0 && ty < RL) { f[ty * 3] = db0; f[ty * 3 + 1] = db1; f[ty * 3 + 2] = db2; }
+        __syncthreads();
+        if (threadIdx.x < 3) {
+            float t = 0.f;
+            for (int j = 0; j < RL; j++) t += f[j * 3 + threadIdx.x];
+            atomicAdd(p.dbias_rgb + threadIdx.x, t);
+        }
+    }
+}
+
+template <bool CONV, bool RGB>
+static int launch_handoff(HandoffParams& p, hipStream_t st) {
+    const dim3 grid = rr_grid(p.B, p.P, p.C, &p.rows_pb);
+    LDETR_CHECK((long)p.rows_pb * p.C < (1L << 30), "sg2_handoff: a row chunk of %d x %d floats exceeds the kernel's 32-bit offsets", p.rows_pb, p.C);
+    const long nblk = (long)grid.x * grid.y;            // dbias is shared by the batch: every block of a channel chunk adds into it
+    const int planes = (CONV ? 1 : 0) + (RGB ? 3 : 0) + 1 + (p.ddemod ? 1 : 0);
+    p.part = nblk > 32 ? scratch_alloc((size_t)planes * nblk * p.C * sizeof(float)) : nullptr;
+    hipLaunchKernelGGL((sg2_handoff_kernel<CONV, RGB>), grid, 256, 0, st, p);
+    int rc = check_launch("sg2_handoff"); if (rc || !p.part) return rc;
+    RRFinish f; memset(&f, 0, sizeof(f));
+    int i = 0;
+    if (CONV) { f.red[i] = p.ds_conv; f.bs[i++] = p.C; }
+    if (RGB) for (int k = 0; k < 3; k++) { f.red[i] = p.dws + (long)k * p.C; f.bs[i++] = 3L * p.C; }
+    f.red[i] = p.dbias; f.bs[i++] = 0;
+    if (p.ddemod) { f.red[i] = p.ddemod; f.bs[i++] = p.C; }
+    f.part = p.part; f.B = p.B; f.C = p.C;
+    return launch_rr_finish(f, planes, (int)grid.x, nblk, st);
 }
 
 }  // namespace ldetr
@@ -501,6 +715,31 @@ extern "C" int ldetr_torgb_bwd_f32(const float* x, const float* dy, const float*
     dim3 grid((unsigned)((P + rows_pb - 1) / rows_pb), B, cdiv(C4, TQ));
     hipLaunchKernelGGL(torgb_bwd_kernel, grid, 256, 0, (hipStream_t)stream, p);
     return check_launch("torgb_bwd");
+}
+
+// dxs (with s_conv, ds_conv) and dy_rgb (with s_rgb, w_rgb, dws_rgb, dbias_rgb) are optional, at least one of them; ddemod (with demod; bias
+// NULL = 0) is optional.  dv may alias dxs.  Every accumulation target must hold its starting value (zeros or a gradient to add to).
+extern "C" int ldetr_sg2_handoff_f32(const float* dxs, const float* x, const float* dy_rgb, float* dv, const float* s_conv, const float* s_rgb,
+                                     const float* w_rgb, const float* bias, const float* demod, float* ds_conv, float* dws_rgb,
+                                     float* dbias_rgb, float* dbias, float* ddemod, int B, int64_t P, int C, float alpha, float gain,
+                                     void* stream) {
+    LDETR_CHECK(x && dv && dbias, "sg2_handoff: x, dv and dbias are required");
+    LDETR_CHECK(dxs || dy_rgb, "sg2_handoff: neither a conv gradient nor an rgb gradient");
+    LDETR_CHECK(!dxs || (s_conv && ds_conv), "sg2_handoff: dxs needs s_conv and ds_conv");
+    LDETR_CHECK(!dy_rgb || (s_rgb && w_rgb && dws_rgb && dbias_rgb), "sg2_handoff: dy_rgb needs s_rgb, w_rgb, dws_rgb and dbias_rgb");
+    LDETR_CHECK(!ddemod || demod, "sg2_handoff: ddemod needs demod");
+    LDETR_CHECK(C % 4 == 0 && C > 0 && B > 0 && P >= 0, "sg2_handoff: C must be a positive multiple of 4, B > 0 (got B %d, C %d)", B, C);
+    LDETR_CHECK((((uintptr_t)dxs | (uintptr_t)x | (uintptr_t)dv | (uintptr_t)s_conv | (uintptr_t)s_rgb | (uintptr_t)w_rgb | (uintptr_t)bias |
+                  (uintptr_t)demod) & 15) == 0, "sg2_handoff: buffers must be 16-byte aligned");
+    if (P == 0) return LDETR_OK;
+    HandoffParams p; memset(&p, 0, sizeof(p));
+    p.dxs = dxs; p.x = x; p.dy = dy_rgb; p.dv = dv; p.s_conv = s_conv; p.s_rgb = s_rgb; p.w_rgb = w_rgb; p.bias = bias; p.demod = demod;
+    p.ds_conv = ds_conv; p.dws = dws_rgb; p.dbias_rgb = dbias_rgb; p.dbias = dbias; p.ddemod = ddemod;
+    p.B = B; p.P = P; p.C = C; p.gp = gain; p.gn = gain * alpha;
+    hipStream_t st = (hipStream_t)stream;
+    if (dxs && dy_rgb) return launch_handoff<true, true>(p, st);
+    if (dxs) return launch_handoff<true, false>(p, st);
+    return launch_handoff<false, true>(p, st);
 }
 
 extern "C" int ldetr_torgb_bwd_finish_f32(const float* dws, const float* s, const float* w, int B, int C, float* dw, float* ds, void* stream) {

@@ -41,6 +41,126 @@ def _prescaled_for_wgrad(x, dv, s, d, B, H):
     return x, dv, s, d
 
 
+def _wgrad_target(wparam, O, KH, KW, I, device):
+    """-> (dw_ohwi, acc): the flat .grad view to accumulate into (acc = 1) or a fresh [O, KH, KW, I] buffer."""
+    gw = core.flat_grad(wparam)
+    if gw is not None and gw.permute(0, 2, 3, 1).is_contiguous():
+        return gw.permute(0, 2, 3, 1), 1
+    return torch.empty((O, KH, KW, I), device=device, dtype=torch.float32), 0
+
+
+# The launches of the three layer kinds, shared by the per-layer Functions below and by the whole-network node (hip/sg2_chain.py).
+def conv_fwd(x, w, s, d, b, pad, act_alpha, act_gain):
+    B, H, W, I = x.shape
+    O, KH, KW, _ = w.shape
+    OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
+    y = torch.empty((B, OH, OW, O), device=x.device, dtype=torch.float32)
+    xt = core.tensor4_nhwc(x)
+    ep = core.epilogue(samp_scale=d, col_bias=b, act=ACT_LRELU, act_alpha=act_alpha, act_gain=act_gain)
+    core.engine_call('ldetr_conv2d_fwd_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_fwd_f32(core.ptr(x), ctypes.byref(xt), core.ptr(w), O, KH, KW, 1, pad, core.ptr(y), O,
+                                               OH, OW, core.ptr(s), s.stride(0), ctypes.byref(ep), core.stream()), 'modconv_fwd'), operands=(x, y, w))
+    return y
+
+
+def conv_bwd_data(dv, w, d, B, H, W, pad):
+    """Data gradient of the 3x3 layer w.r.t. its styled input (the `* styles` is the caller's)."""
+    O, KH, KW, I = w.shape
+    _, OH, OW, _ = dv.shape
+    dvt = core.tensor4_nhwc(dv)
+    dxs = torch.empty((B, H, W, I), device=dv.device, dtype=torch.float32)
+    core.engine_call('ldetr_conv2d_bwd_data_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_bwd_data_f32(core.ptr(dv), ctypes.byref(dvt), core.ptr(w), I, KH, KW, 1, pad,
+                                                    core.ptr(dxs), I, H, W, core.ptr(d), d.stride(0), None, core.stream()),
+               'modconv_bwd_data'), operands=(dv, dxs, w))
+    return dxs
+
+
+def conv_bwd_weight(x, dv, w, s, d, wparam, pad):
+    """-> dw (logical OIHW) or None when it was accumulated into the flat gradient buffer."""
+    B, H, W, I = x.shape
+    O, KH, KW, _ = w.shape
+    _, OH, OW, _ = dv.shape
+    dw_ohwi, acc = _wgrad_target(wparam, O, KH, KW, I, dv.device)
+    sk = 0   # the library picks tile and split-K factor together
+    xw, dvw, sw, dw_ = _prescaled_for_wgrad(x, dv, s, d, B, H)
+    xwt, dvwt = core.tensor4_nhwc(xw), core.tensor4_nhwc(dvw)     # descriptors of the tensors actually passed
+    core.engine_call('ldetr_conv2d_bwd_weight_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xwt), core.ptr(dvw), ctypes.byref(dvwt),
+                                                      core.ptr(dw_ohwi), KH, KW, 1, pad, sk, core.ptr(sw), sw.stride(0) if sw is not None else 0,
+                                                      core.ptr(dw_), dw_.stride(0) if dw_ is not None else 0, acc, core.stream()), 'modconv_bwd_weight'), operands=(x, dv, dw_ohwi))
+    return None if acc else _grad_to_oihw(dw_ohwi)
+
+
+def up_fwd(x, w, s, d, b, f, act_alpha, act_gain):
+    """-> (ud, y): the demodulated transposed convolution and the layer's output."""
+    B, H, W, I = x.shape
+    O, KH, KW, _ = w.shape
+    UH, UW = (H - 1) * 2 + KH, (W - 1) * 2 + KW
+    ud = torch.empty((B, UH, UW, O), device=x.device, dtype=torch.float32)
+    xt = core.tensor4_nhwc(x)
+    ep = core.epilogue(samp_scale=d)
+    core.engine_call('ldetr_conv_transpose2d_fwd_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_fwd_f32(core.ptr(x), ctypes.byref(xt), core.ptr(w), O, KH, KW, 2, 0, core.ptr(ud),
+                                                         O, UH, UW, core.ptr(s), s.stride(0), ctypes.byref(ep), core.stream()),
+               'modconv_up_fwd'), operands=(x, ud, w))
+    # conv2d_resample.py:113-130 with padding=1, 4-tap filter, up=2 -> transposed-conv pad 0, FIR pad [1,1,1,1], gain 4
+    y = _up._kernel_call(ud.permute(0, 3, 1, 2), f, 1, 1, 1, 1, 1, 1, 1, 1, False, 4.0, act_bias=b,
+                         act=(act_alpha, act_gain)).permute(0, 2, 3, 1)
+    return ud, y
+
+
+def up_fir_adjoint(dv, f):
+    # adjoint of the FIR (upfirdn2d.py:252-270): flipped taps, pad [fw-px0-1, iw-ow+px0, ...] = [2,2,2,2]
+    return _up._kernel_call(dv.permute(0, 3, 1, 2), f, 1, 1, 1, 1, 2, 2, 2, 2, True, 4.0).permute(0, 2, 3, 1)
+
+
+def up_bwd_data(dud, w, d, B, H, W):
+    O, KH, KW, I = w.shape
+    dudt = core.tensor4_nhwc(dud)
+    dxs = torch.empty((B, H, W, I), device=dud.device, dtype=torch.float32)
+    core.engine_call('ldetr_conv_transpose2d_bwd_data_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_bwd_data_f32(core.ptr(dud), ctypes.byref(dudt), core.ptr(w), I, KH, KW, 2, 0,
+                                                              core.ptr(dxs), I, H, W, core.ptr(d), d.stride(0), None,
+                                                              core.stream()), 'modconv_up_bwd_data'), operands=(dud, dxs, w))
+    return dxs
+
+
+def up_bwd_weight(x, dud, w, s, d, wparam):
+    B, H, W, I = x.shape
+    O, KH, KW, _ = w.shape
+    dw_ohwi, acc = _wgrad_target(wparam, O, KH, KW, I, dud.device)
+    sk = 0   # the library picks tile and split-K factor together
+    xw, dudw, sw, dw_ = _prescaled_for_wgrad(x, dud, s, d, B, H)
+    xwt, dudwt = core.tensor4_nhwc(xw), core.tensor4_nhwc(dudw)   # descriptors of the tensors actually passed
+    core.engine_call('ldetr_conv_transpose2d_bwd_weight_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xwt), core.ptr(dudw), ctypes.byref(dudwt),
+                                                                core.ptr(dw_ohwi), KH, KW, 2, 0, sk, core.ptr(sw), sw.stride(0) if sw is not None else 0,
+                                                                core.ptr(dw_), dw_.stride(0) if dw_ is not None else 0, acc, core.stream()), 'modconv_up_bwd_weight'), operands=(x, dud, dw_ohwi))
+    return None if acc else _grad_to_oihw(dw_ohwi)
+
+
+def torgb_fwd(x, w, s, b):
+    """x [B, H, W, C], w [3, C] -> [B, H, W, 3]."""
+    B, H, W, C = x.shape
+    O = w.shape[0]
+    y = torch.empty((B, H, W, O), device=x.device, dtype=torch.float32)
+    c4 = C // 4
+    if O == 3 and C % 4 == 0 and C <= 512 and (c4 & (c4 - 1)) == 0 and s.stride(0) == C:
+        # streaming kernel (csrc/misc_ops.hip): one read of x; on the engine the 3 output channels pad a 64-wide tile (144 us at 16 x 256^2 x 32)
+        core.check(core.lib().ldetr_torgb_fwd_f32(core.ptr(x), core.ptr(w), core.ptr(s), core.ptr(b), core.ptr(y), B, H * W, C, core.stream()), 'torgb_fwd')
+    else:
+        xt = core.tensor4_nhwc(x)
+        ep = core.epilogue(col_bias=b)
+        core.engine_call('ldetr_conv2d_fwd_f32', 2.0 * B * H * W * O * C, lambda: core.check(core.lib().ldetr_conv2d_fwd_f32(core.ptr(x), ctypes.byref(xt), core.ptr(w), O, 1, 1, 1, 0, core.ptr(y), O, H, W,
+                                                   core.ptr(s), s.stride(0), ctypes.byref(ep), core.stream()), 'torgb_fwd'), operands=(x, y, w))
+    return y
+
+
+def torgb_grad_targets(wparam, bparam, O, C, device):
+    """Weight / bias gradients of a toRGB go straight into the flat .grad views when there are any (atomics / += in the kernels): no temporaries, no
+    AccumulateGrad launches.  -> (dw [O, C], dbias [O], weight is flat, bias is flat)."""
+    gw, gb = core.flat_grad(wparam), core.flat_grad(bparam)
+    gw = gw.reshape(O, C) if (gw is not None and gw.is_contiguous()) else None
+    dbias = gb if gb is not None else torch.zeros(O, device=device, dtype=torch.float32)
+    dw = gw if gw is not None else torch.zeros((O, C), device=device, dtype=torch.float32)
+    return dw, dbias, gw is not None, gb is not None
+
+
 class _ModConvFn(torch.autograd.Function):
     """y = lrelu(conv3x3(x * s) * d + bias) * gain      (up == 1)"""
 
@@ -48,14 +168,7 @@ class _ModConvFn(torch.autograd.Function):
     def forward(ctx, x, weight, styles, dcoefs, bias, pad, act_alpha, act_gain):
         core.require_gpu(x, weight, styles, dcoefs, bias)
         x = core.f32c(x); w = core.f32c(weight_ohwi(weight)); s = core.f32c(styles); d = core.f32c(dcoefs); b = core.f32c(bias)
-        B, H, W, I = x.shape
-        O, KH, KW, _ = w.shape
-        OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
-        y = torch.empty((B, OH, OW, O), device=x.device, dtype=torch.float32)
-        xt = core.tensor4_nhwc(x)
-        ep = core.epilogue(samp_scale=d, col_bias=b, act=ACT_LRELU, act_alpha=act_alpha, act_gain=act_gain)
-        core.engine_call('ldetr_conv2d_fwd_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_fwd_f32(core.ptr(x), ctypes.byref(xt), core.ptr(w), O, KH, KW, 1, pad, core.ptr(y), O,
-                                                   OH, OW, core.ptr(s), s.stride(0), ctypes.byref(ep), core.stream()), 'modconv_fwd'), operands=(x, y, w))
+        y = conv_fwd(x, w, s, d, b, pad, act_alpha, act_gain)
         ctx.save_for_backward(x, w, s, d, b, y)
         ctx.cfg = (pad, act_alpha, act_gain)
         ctx.params = (weight, bias)
@@ -73,28 +186,12 @@ class _ModConvFn(torch.autograd.Function):
         dv2, dbias, ddemod = act_backward(dy.reshape(-1, O), y.reshape(-1, O), ACT_LRELU, act_alpha, act_gain, True,
                                           bias=b, demod=d, want_ddemod=True, B=B, dbias_out=core.flat_grad(bparam))
         dv = dv2.reshape(B, OH, OW, O)
-        dvt = core.tensor4_nhwc(dv)
         dx = dw = ds = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
-            dxs = torch.empty((B, H, W, I), device=dy.device, dtype=torch.float32)
-            core.engine_call('ldetr_conv2d_bwd_data_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_bwd_data_f32(core.ptr(dv), ctypes.byref(dvt), core.ptr(w), I, KH, KW, 1, pad,
-                                                            core.ptr(dxs), I, H, W, core.ptr(d), d.stride(0), None, core.stream()),
-                       'modconv_bwd_data'), operands=(dv, dxs, w))
+            dxs = conv_bwd_data(dv, w, d, B, H, W, pad)
             dx, ds = _mul_reduce(dxs, x, s, B, H * W, I)
         if ctx.needs_input_grad[1]:
-            gw = core.flat_grad(wparam)
-            acc = 0
-            if gw is not None and gw.permute(0, 2, 3, 1).is_contiguous():
-                dw_ohwi, acc = gw.permute(0, 2, 3, 1), 1
-            else:
-                dw_ohwi = torch.empty((O, KH, KW, I), device=dy.device, dtype=torch.float32)
-            sk = 0   # the library picks tile and split-K factor together
-            xw, dvw, sw, dw_ = _prescaled_for_wgrad(x, dv, s, d, B, H)
-            xwt, dvwt = core.tensor4_nhwc(xw), core.tensor4_nhwc(dvw)     # descriptors of the tensors actually passed
-            core.engine_call('ldetr_conv2d_bwd_weight_f32', 2.0 * B * OH * OW * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xwt), core.ptr(dvw), ctypes.byref(dvwt),
-                                                              core.ptr(dw_ohwi), KH, KW, 1, pad, sk, core.ptr(sw), sw.stride(0) if sw is not None else 0,
-                                                              core.ptr(dw_), dw_.stride(0) if dw_ is not None else 0, acc, core.stream()), 'modconv_bwd_weight'), operands=(x, dv, dw_ohwi))
-            dw = None if acc else _grad_to_oihw(dw_ohwi)
+            dw = conv_bwd_weight(x, dv, w, s, d, wparam, pad)
         return dx, dw, ds, ddemod, dbias, None, None, None
 
 
@@ -105,61 +202,32 @@ class _ModConvUpFn(torch.autograd.Function):
     def forward(ctx, x, weight, styles, dcoefs, bias, f, act_alpha, act_gain):
         core.require_gpu(x, weight, styles, dcoefs, bias, f)
         x = core.f32c(x); w = core.f32c(weight_ohwi(weight)); s = core.f32c(styles); d = core.f32c(dcoefs); b = core.f32c(bias)
-        B, H, W, I = x.shape
-        O, KH, KW, _ = w.shape
-        UH, UW = (H - 1) * 2 + KH, (W - 1) * 2 + KW
-        ud = torch.empty((B, UH, UW, O), device=x.device, dtype=torch.float32)
-        xt = core.tensor4_nhwc(x)
-        ep = core.epilogue(samp_scale=d)
-        core.engine_call('ldetr_conv_transpose2d_fwd_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_fwd_f32(core.ptr(x), ctypes.byref(xt), core.ptr(w), O, KH, KW, 2, 0, core.ptr(ud),
-                                                             O, UH, UW, core.ptr(s), s.stride(0), ctypes.byref(ep), core.stream()),
-                   'modconv_up_fwd'), operands=(x, ud, w))
-        # conv2d_resample.py:113-130 with padding=1, 4-tap filter, up=2 -> transposed-conv pad 0, FIR pad [1,1,1,1], gain 4
-        y = _up._kernel_call(ud.permute(0, 3, 1, 2), f, 1, 1, 1, 1, 1, 1, 1, 1, False, 4.0, act_bias=b,
-                             act=(act_alpha, act_gain)).permute(0, 2, 3, 1)
-        ctx.save_for_backward(x, w, s, d, b, f, ud, y)
+        _, y = up_fwd(x, w, s, d, b, f, act_alpha, act_gain)
+        # (ud, the transposed convolution's output, is not kept: the backward needs it only in <dud, ud>, and that sum equals
+        # <dv, pre(y) - bias> because 4 FIR(ud) = pre(y) - bias and dud = 4 FIR^T(dv): the sum act_backward forms from y anyway)
+        ctx.save_for_backward(x, w, s, d, b, f, y)
         ctx.cfg = (act_alpha, act_gain)
         ctx.params = (weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, s, d, b, f, ud, y = ctx.saved_tensors
+        x, w, s, d, b, f, y = ctx.saved_tensors
         act_alpha, act_gain = ctx.cfg
         B, H, W, I = x.shape
         O, KH, KW, _ = w.shape
-        _, UH, UW, _ = ud.shape
         dy = core.f32c(dy)
         wparam, bparam = ctx.params
-        dv2, dbias, _ = act_backward(dy.reshape(-1, O), y.reshape(-1, O), ACT_LRELU, act_alpha, act_gain, True,
-                                     dbias_out=core.flat_grad(bparam))
+        dv2, dbias, ddemod = act_backward(dy.reshape(-1, O), y.reshape(-1, O), ACT_LRELU, act_alpha, act_gain, True,
+                                          bias=b, demod=d, want_ddemod=True, B=B, dbias_out=core.flat_grad(bparam))
         dv = dv2.reshape(y.shape)
-        # adjoint of the FIR (upfirdn2d.py:252-270): flipped taps, pad [fw-px0-1, iw-ow+px0, ...] = [2,2,2,2]
-        dud = _up._kernel_call(dv.permute(0, 3, 1, 2), f, 1, 1, 1, 1, 2, 2, 2, 2, True, 4.0).permute(0, 2, 3, 1)
-        _, dd_num = _mul_reduce(dud, ud, None, B, UH * UW, O, want_out=False)
-        ddemod = dd_num / d
-        dudt = core.tensor4_nhwc(dud)
+        dud = up_fir_adjoint(dv, f)
         dx = dw = ds = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
-            dxs = torch.empty((B, H, W, I), device=dy.device, dtype=torch.float32)
-            core.engine_call('ldetr_conv_transpose2d_bwd_data_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_bwd_data_f32(core.ptr(dud), ctypes.byref(dudt), core.ptr(w), I, KH, KW, 2, 0,
-                                                                      core.ptr(dxs), I, H, W, core.ptr(d), d.stride(0), None,
-                                                                      core.stream()), 'modconv_up_bwd_data'), operands=(dud, dxs, w))
+            dxs = up_bwd_data(dud, w, d, B, H, W)
             dx, ds = _mul_reduce(dxs, x, s, B, H * W, I)
         if ctx.needs_input_grad[1]:
-            gw = core.flat_grad(wparam)
-            acc = 0
-            if gw is not None and gw.permute(0, 2, 3, 1).is_contiguous():
-                dw_ohwi, acc = gw.permute(0, 2, 3, 1), 1
-            else:
-                dw_ohwi = torch.empty((O, KH, KW, I), device=dy.device, dtype=torch.float32)
-            sk = 0   # the library picks tile and split-K factor together
-            xw, dudw, sw, dw_ = _prescaled_for_wgrad(x, dud, s, d, B, H)
-            xwt, dudwt = core.tensor4_nhwc(xw), core.tensor4_nhwc(dudw)   # descriptors of the tensors actually passed
-            core.engine_call('ldetr_conv_transpose2d_bwd_weight_f32', 2.0 * B * H * W * O * KH * KW * I, lambda: core.check(core.lib().ldetr_conv_transpose2d_bwd_weight_f32(core.ptr(xw), ctypes.byref(xwt), core.ptr(dudw), ctypes.byref(dudwt),
-                                                                        core.ptr(dw_ohwi), KH, KW, 2, 0, sk, core.ptr(sw), sw.stride(0) if sw is not None else 0,
-                                                                        core.ptr(dw_), dw_.stride(0) if dw_ is not None else 0, acc, core.stream()), 'modconv_up_bwd_weight'), operands=(x, dud, dw_ohwi))
-            dw = None if acc else _grad_to_oihw(dw_ohwi)
+            dw = up_bwd_weight(x, dud, w, s, d, wparam)
         return dx, dw, ds, ddemod, dbias, None, None, None
 
 
@@ -171,18 +239,7 @@ class _ToRGBFn(torch.autograd.Function):
         core.require_gpu(x, weight, styles, bias)
         x = core.f32c(x); s = core.f32c(styles); b = core.f32c(bias)
         w = core.f32c(weight.reshape(weight.shape[0], -1))  # [3, C]
-        B, H, W, C = x.shape
-        O = w.shape[0]
-        y = torch.empty((B, H, W, O), device=x.device, dtype=torch.float32)
-        c4 = C // 4
-        if O == 3 and C % 4 == 0 and C <= 512 and (c4 & (c4 - 1)) == 0 and s.stride(0) == C:
-            # streaming kernel (csrc/misc_ops.hip): one read of x; on the engine the 3 output channels pad a 64-wide tile (144 us at 16 x 256^2 x 32)
-            core.check(core.lib().ldetr_torgb_fwd_f32(core.ptr(x), core.ptr(w), core.ptr(s), core.ptr(b), core.ptr(y), B, H * W, C, core.stream()), 'torgb_fwd')
-        else:
-            xt = core.tensor4_nhwc(x)
-            ep = core.epilogue(col_bias=b)
-            core.engine_call('ldetr_conv2d_fwd_f32', 2.0 * B * H * W * O * C, lambda: core.check(core.lib().ldetr_conv2d_fwd_f32(core.ptr(x), ctypes.byref(xt), core.ptr(w), O, 1, 1, 1, 0, core.ptr(y), O, H, W,
-                                                       core.ptr(s), s.stride(0), ctypes.byref(ep), core.stream()), 'torgb_fwd'), operands=(x, y, w))
+        y = torgb_fwd(x, w, s, b)
         ctx.save_for_backward(x, w, s)
         ctx.wshape = weight.shape
         ctx.params = (weight, bias)
@@ -198,18 +255,14 @@ class _ToRGBFn(torch.autograd.Function):
         dy = core.f32c(dy)
         dx = torch.empty_like(x)
         dws = core.zeros((B, O, C), x.device)
-        # weight / bias gradients go straight into the flat .grad views when there are any (atomics / += in the kernels): no temporaries, no
-        # AccumulateGrad launches; ds and dw come out of one finish launch instead of two broadcast multiplies + two reductions
+        # ds and dw come out of one finish launch instead of two broadcast multiplies + two reductions
         wparam, bparam = ctx.params
-        gw, gb = core.flat_grad(wparam), core.flat_grad(bparam)
-        gw = gw.reshape(O, C) if (gw is not None and gw.is_contiguous()) else None
-        dbias = gb if gb is not None else torch.zeros(O, device=x.device, dtype=torch.float32)
-        dw = gw if gw is not None else torch.zeros((O, C), device=x.device, dtype=torch.float32)
+        dw, dbias, w_flat, b_flat = torgb_grad_targets(wparam, bparam, O, C, x.device)
         ds = torch.empty((B, C), device=x.device, dtype=torch.float32)
         core.check(core.lib().ldetr_torgb_bwd_f32(core.ptr(x), core.ptr(dy), core.ptr(w), core.ptr(s), core.ptr(dx), core.ptr(dws),
                                                   core.ptr(dbias), B, H * W, C, core.stream()), 'torgb_bwd')
         core.check(core.lib().ldetr_torgb_bwd_finish_f32(core.ptr(dws), core.ptr(s), core.ptr(w), B, C, core.ptr(dw), core.ptr(ds), core.stream()), 'torgb_bwd_finish')
-        return dx, (None if gw is not None else dw.reshape(ctx.wshape)), ds, (None if gb is not None else dbias)
+        return dx, (None if w_flat else dw.reshape(ctx.wshape)), ds, (None if b_flat else dbias)
 
 
 class _DemodFn(torch.autograd.Function):

@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from ..hip import core, modconv
+from ..hip import core, modconv, sg2_chain
 from ..hip.linear import linear
 from ..torch_utils.ops import bias_act, upfirdn2d
 
@@ -192,6 +192,8 @@ class SynthesisNetwork(torch.nn.Module):
         """ws: [B, num_ws, w_dim] (one latent per layer, the reference's form) or [B, w_dim] (the same latent for every layer — what
         the Decoder's mapping network produces: handed over without materialising the num_ws copies)."""
         ws = ws.to(torch.float32)
+        if sg2_chain.ENABLED and not (set(block_kwargs) - {'update_emas', 'noise_mode', 'force_fp32'}):
+            return self._forward_node(ws)
         x = img = None
         first = 0
         for res in self.block_resolutions:
@@ -200,6 +202,31 @@ class SynthesisNetwork(torch.nn.Module):
             cur = ws.unsqueeze(1).expand(-1, n, -1) if ws.ndim == 2 else ws[:, first:first + n]
             x, img = block(x, img, cur, **block_kwargs)
             first += block.num_conv
+        return img.permute(0, 3, 1, 2)  # [B, 3, R, R] view (channels_last memory)
+
+
+    def _forward_node(self, ws):
+        """The whole network as one autograd node (hip/sg2_chain.py): the affines and the demodulation coefficients per layer here, under
+        ordinary autograd, in the order the blocks' forwards compute them; the convolutions and everything between them inside the node."""
+        blocks, tensors = [], []
+        first = 0
+        for res in self.block_resolutions:
+            block = getattr(self, f'b{res}')
+            n = block.num_conv + block.num_torgb          # the block's toRGB shares its latent with the next block's first conv
+            w_iter = iter([ws] * n if ws.ndim == 2 else ws[:, first:first + n].unbind(dim=1))
+            layers = ([block.conv0] if block.in_channels != 0 else []) + [block.conv1]
+            for layer in layers:
+                styles = layer.affine(next(w_iter))
+                tensors += [layer.weight, layer.bias, styles, modconv.demod_coefs(layer.weight, styles)]
+            tensors += [block.torgb.weight, block.torgb.bias, block.torgb.affine(next(w_iter)) * float(block.torgb.weight_gain)]
+            gains = (float(block.conv0.act_gain) if block.in_channels != 0 else None, float(block.conv1.act_gain))
+            params = {'conv1': (block.conv1.weight, block.conv1.bias), 'torgb': (block.torgb.weight, block.torgb.bias)}
+            if block.in_channels != 0:
+                params['conv0'] = (block.conv0.weight, block.conv0.bias)
+            blocks.append(sg2_chain.Block(block.in_channels != 0, gains, params))
+            first += block.num_conv
+        b4 = getattr(self, f'b{self.block_resolutions[0]}')
+        img = sg2_chain.run(blocks, b4.const, b4.resample_filter, tensors)
         return img.permute(0, 3, 1, 2)  # [B, 3, R, R] view (channels_last memory)
 
 
