@@ -34,6 +34,9 @@
  *                                 PIL resize + normalise of the page background: training/dataset_layoutganpp.py:330-338
  *   ldetr_page_filter_u8          ImageFilter.GaussianBlur / convert('L').filter(FIND_EDGES).convert('RGB') of the page background:
  *                                 generate.py:267-269, 280-282
+ *   ldetr_png_scan, ldetr_png_decode_u8
+ *                                 PIL.Image.open + np.array of a page PNG written with compress_level=0: dataset_tool.py:325-363,
+ *                                 training/dataset_layoutganpp.py:329-340
  *   ldetr_resample_coeffs_filter, ldetr_layout_raster_cell_size, ldetr_layout_raster_u8
  *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
  *   ldetr_patch_resize_u8, ldetr_image_raster_u8
@@ -535,6 +538,48 @@ typedef struct ldetr_image_raster_args {
 } ldetr_image_raster_args;
 int ldetr_patch_resize_u8(const ldetr_patch_resize_args* a, void* stream);
 int ldetr_image_raster_u8(const ldetr_image_raster_args* a, void* stream);
+
+/* The page PNGs of the dataset decoded on the device (csrc/png_decode.hip).  dataset_tool.py:325-363 saves every PNG with
+ * compress_level=0, optimize=False, so its zlib stream holds stored blocks only; what dataset_layoutganpp.py:329-340 gets from PIL.Image.open + np.array
+ * is then a copy of the stored payloads and PNG's per-row filter undone.  Bit-identical to Pillow.
+ * ldetr_png_scan (HOST memory, no GPU work; dataset_tool.py:325-363, dataset_layoutganpp.py:329-340): walks the chunks (signature, IHDR, ancillary
+ * chunks, IDAT run, IEND) and the zlib stream across IDAT boundaries (the 2-byte header, a 5-byte stored-block header and the Adler-32 may each be split
+ * over chunks) of one file.  Outputs width, height, channels; segments [k][3] = (offset in file, offset in the filtered scanline stream, length), one
+ * per contiguous run of stored payload; row_starts [r] (optional): row 0 and every row with filter 0 / 1 at least 64 rows after the previous entry -- a
+ * row range that starts there reads nothing above it.  Call with segments = NULL (row_starts = NULL) to query the counts; a table that is given and
+ * too small is LDETR_ERR_ARG.  Returns 0 (eligible), LDETR_PNG_NOT_ELIGIBLE (a well-formed PNG the device path does not take: a non-stored deflate
+ * block, interlace, palette, 16-bit, grey / grey-alpha / RGBA, a preset dictionary, wider than 4096 or taller than 32768) or LDETR_PNG_MALFORMED
+ * (truncated, bad signature, chunk length past the end, LEN != ~NLEN, payload != H * (1 + 3 W), a filter byte > 4, no IEND); the message is
+ * ldetr_last_error().  Chunk CRC-32 and the Adler-32 are not checked here.
+ * ldetr_png_decode_u8 (dataset_tool.py:325-363, dataset_layoutganpp.py:329-340): n files of ONE page size -> dst [n][H][W][3], at most two launches:
+ * a gather of the payload runs into scratch [n][H][1 + 3 W], then the unfilter, one workgroup per row range.  The entry validates the HOST tables
+ * before any launch (every segment inside its file, the stream offsets of each page tiling H * (1 + 3 W) exactly and in order, the row ranges of each
+ * page tiling [0, H) in order, 1 <= W <= 4096, 1 <= H <= 32768) and returns an error instead of launching otherwise; the kernels read the device
+ * copies and clamp every index to the buffers.  A row range must start at a row ldetr_png_scan listed (the kernel sees zeros above it). */
+#define LDETR_PNG_NOT_ELIGIBLE 3
+#define LDETR_PNG_MALFORMED 4
+typedef struct ldetr_png_decode_args {
+    int struct_bytes;             /* sizeof(ldetr_png_decode_args) as the caller sees it */
+    int n, H, W;
+    int phases;                   /* 1 gather only, 2 unfilter only (scratch already gathered), 3 both: the benchmark times the two apart */
+    int reserved;
+    const uint8_t* files;         /* device: the files, concatenated; 16-byte aligned */
+    int64_t files_bytes;          /* a multiple of 16 (pad the buffer) */
+    const int64_t* file_off;      /* HOST [n + 1]: byte offset of file i, file_off[n] = end of the last file */
+    const int64_t* file_off_dev;  /* device: the same */
+    const int64_t* segments;      /* HOST [n_segments][4] = (page, offset in file, offset in stream, length), pages in order */
+    const int64_t* segments_dev;  /* device: the same */
+    int64_t n_segments;
+    const int32_t* jobs;          /* HOST [n_jobs][3] = (page, first row, end row), pages in order */
+    const int32_t* jobs_dev;      /* device: the same */
+    int64_t n_jobs;
+    uint8_t* scratch;             /* device, 16-byte aligned */
+    int64_t scratch_bytes;        /* a multiple of 16, >= n * H * (1 + 3 W) */
+    uint8_t* dst;                 /* device [n][H][W][3], 4-byte aligned */
+} ldetr_png_decode_args;
+int ldetr_png_scan(const uint8_t* file, int64_t file_bytes, int* width, int* height, int* channels, int64_t* segments, int64_t segments_capacity,
+                   int64_t* segments_count, int32_t* row_starts, int64_t row_starts_capacity, int64_t* row_starts_count);
+int ldetr_png_decode_u8(const ldetr_png_decode_args* a, void* stream);
 
 /* Batched linear-sum-assignment (Hungarian / shortest augmenting path) on device.
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;

@@ -101,6 +101,15 @@ class ImageRasterArgs(Structure):
                 ('cells_dev', c_void_p), ('out', c_void_p)]
 
 
+class PngDecodeArgs(Structure):
+    """ldetr_png_decode_args."""
+    _fields_ = [('struct_bytes', c_int), ('n', c_int), ('H', c_int), ('W', c_int), ('phases', c_int), ('reserved', c_int),
+                ('files', c_void_p), ('files_bytes', c_int64), ('file_off', c_void_p), ('file_off_dev', c_void_p),
+                ('segments', c_void_p), ('segments_dev', c_void_p), ('n_segments', c_int64),
+                ('jobs', c_void_p), ('jobs_dev', c_void_p), ('n_jobs', c_int64),
+                ('scratch', c_void_p), ('scratch_bytes', c_int64), ('dst', c_void_p)]
+
+
 _P = c_void_p
 _I = c_int
 _L = c_int64
@@ -191,6 +200,8 @@ SIGNATURES = {
     'ldetr_struct_sizes': [_P],
     'ldetr_resize_normalize_u8': [_P, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P],
     'ldetr_page_filter_u8': [_P, _P, _L, _I, _I, _I, _F, _P],
+    'ldetr_png_scan': [_P, _L, _P, _P, _P, _P, _L, _P, _P, _L, _P],
+    'ldetr_png_decode_u8': [_P, _P],
 }
 
 _lib = None

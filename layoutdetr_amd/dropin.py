@@ -165,16 +165,32 @@ def install_plugins():
     return custom_ops._cached_plugins
 
 
-def main(argv):
-    import os
+DATASET_MODE_ENV = 'LDETR_DATASET_MODE'       # read by training/dataset_layoutganpp.py where a LayoutDataset is built without an explicit mode
+
+
+def parse_options(argv, environ):
+    """The options in front of the script: each sets the environment variable the training code reads; returns what is left of argv.
+    --image-snapshot-kinds: which snapshot kinds training_loop writes (training/snapshot_images.py);
+    --dataset-mode: 'device' (Pillow decodes the page on the host) or 'raw' (the page's PNG bytes go to the GPU and are decoded there)."""
     argv = list(argv)
-    while argv and argv[0].startswith('--image-snapshot-kinds'):      # before the script: which snapshot kinds training_loop writes (training/snapshot_images.py)
+    while argv and (argv[0].startswith('--image-snapshot-kinds') or argv[0].startswith('--dataset-mode')):
         opt = argv.pop(0)
         value = opt.split('=', 1)[1] if '=' in opt else (argv.pop(0) if argv else '')
-        from .training.snapshot_images import KINDS_ENV, parse_kinds
-        os.environ[KINDS_ENV] = ','.join(parse_kinds(value))
+        if opt.startswith('--image-snapshot-kinds'):
+            from .training.snapshot_images import KINDS_ENV, parse_kinds
+            environ[KINDS_ENV] = ','.join(parse_kinds(value))
+        else:
+            if value not in ('device', 'raw'):
+                raise SystemExit(f"--dataset-mode: 'device' or 'raw' (got {value!r})")
+            environ[DATASET_MODE_ENV] = value
+    return argv
+
+
+def main(argv):
+    import os
+    argv = parse_options(argv, os.environ)
     if not argv:
-        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] <script.py> [script args...]')
+        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] [--dataset-mode=device|raw] <script.py> [script args...]')
     sys.path.insert(0, os.path.dirname(os.path.abspath(argv[0])))
     for pkg in ('training', 'torch_utils', 'torch_utils.ops'):     # import the reference's packages first so aliases attach to them
         try:

@@ -17,6 +17,12 @@ nine slots with a validity mask (`to_dense_batch`, :29-41).
   the `images` snapshot kinds read their uint8 crops through `patch_crops(idx)` instead.
   `LayoutDataset.collate` keeps the pages uint8 and the patch placeholder 0-stride (torch's default collate would materialise 7 MB
   of zeros per sample); `training_loop()` passes it to the DataLoader and calls `batch_backgrounds_to_device`.
+* mode='raw' (opt-in; `LDETR_DATASET_MODE=raw`, `python -m layoutdetr_amd.dropin --dataset-mode=raw`): as 'device' in every key except
+  'background', which is the page's PNG FILE BYTES (`RawPage`: the zip entries are ZIP_STORED, a read) when `scan_png` finds the file
+  eligible -- 8-bit RGB, not interlaced, a zlib stream of stored blocks only, which is what the reference's dataset_tool.py:325-363 writes
+  (compress_level=0) -- and the Pillow-decoded uint8 page, exactly as 'device' produces it, otherwise (a per-item fallback, counted in
+  `route_counts`).  `batch_backgrounds_to_device` decodes the raw pages of a batch on the GPU (`decode_pages`, csrc/png_decode.hip: a gather of
+  the stored payload + PNG's row filters undone, bit-identical to Pillow) and proceeds as for 'device'.
 * mode='reference': every key of the reference's item, computed on the host exactly as the reference does (PIL decode + Lanczos
   resize, float normalise, transpose) — what `setup_snapshot` (training_loop.py:36-59) needs, and the side that
   tests/golden/dataset.npz (the reference's own `__getitem__` on tests/golden/dataset_tiny.zip) pins.
@@ -24,9 +30,12 @@ nine slots with a validity mask (`to_dense_batch`, :29-41).
 Device side (`background_to_tensor`, `csrc/resample.hip`): there is no CPU fallback — without the HIP library or a GPU tensor it raises.
 """
 import ctypes
+import io
 import json
 import os
+import struct
 import zipfile
+import zlib
 
 import numpy as np
 import torch
@@ -114,6 +123,158 @@ def background_to_tensor(pages_u8, background_size, return_u8=False, mean=RGB_ME
         out = out[0]
         u8 = u8[0] if u8 is not None else None
     return (out, u8) if return_u8 else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stored-block PNG pages: host scan + device decode (csrc/png_decode.hip)
+
+DATASET_MODES = ('device', 'raw', 'reference')
+PNG_NOT_ELIGIBLE, PNG_MALFORMED = 3, 4                  # include/ldetr_hip.h LDETR_PNG_*
+
+
+def default_dataset_mode():
+    """The mode a `LayoutDataset` built without an explicit `mode` takes: LDETR_DATASET_MODE (set by `dropin --dataset-mode`), else 'device'."""
+    mode = os.environ.get('LDETR_DATASET_MODE') or 'device'
+    if mode not in DATASET_MODES:
+        raise ValueError(f'LDETR_DATASET_MODE={mode!r}: one of {DATASET_MODES}')
+    return mode
+
+
+class RawPage:
+    """One eligible page PNG as `scan_png` found it: `data` the file bytes (1-D uint8, numpy or a CPU torch tensor), `width`, `height`,
+    `segments` int64 [k, 3] = (offset in file, offset in the filtered scanline stream, length) and `row_starts` int32 [r], the rows at
+    which `decode_pages` starts an independent row range."""
+    __slots__ = ('data', 'width', 'height', 'segments', 'row_starts')
+
+    def __init__(self, data, width, height, segments, row_starts):
+        self.data, self.width, self.height, self.segments, self.row_starts = data, int(width), int(height), segments, row_starts
+
+    shape = property(lambda self: (self.height, self.width, 3))          # of the decoded page
+
+    def tensor(self):
+        return self.data if torch.is_tensor(self.data) else torch.from_numpy(self.data)
+
+    def pin_memory(self, device=None):
+        """What DataLoader(pin_memory=True) calls on a batch element: the file bytes in page-locked memory, the tables as they are."""
+        return RawPage(self.tensor().pin_memory(), self.width, self.height, self.segments, self.row_starts)
+
+
+def _verify_png(data):
+    """Chunk CRC-32s and the zlib stream's Adler-32 of a file `ldetr_png_scan` accepted, as Pillow checks them."""
+    buf = data.tobytes()
+    pos, idat = 8, []
+    while pos + 12 <= len(buf):
+        n, = struct.unpack('>I', buf[pos:pos + 4])
+        crc, = struct.unpack('>I', buf[pos + 8 + n:pos + 12 + n])
+        if zlib.crc32(buf[pos + 4:pos + 8 + n]) != crc:
+            raise ValueError(f'scan_png: chunk {buf[pos + 4:pos + 8]!r} at byte {pos}: CRC-32 mismatch')
+        if buf[pos + 4:pos + 8] == b'IDAT':
+            idat.append(buf[pos + 8:pos + 8 + n])
+        if buf[pos + 4:pos + 8] == b'IEND':
+            break
+        pos += 12 + n
+    return b''.join(idat)
+
+
+def scan_png(data, verify=False):
+    """One PNG file (bytes, or a 1-D uint8 array) -> `RawPage` when the device path takes it, None when it is a well-formed PNG that it does
+    not take (compressed blocks, interlace, palette, 16-bit, grey / RGBA, ...: the caller decodes those with Pillow); ValueError for a malformed
+    file.  Host work only (`ldetr_png_scan`).  verify=True also checks every chunk's CRC-32 and the stream's Adler-32, which Pillow does and the
+    scan does not, and raises ValueError on a mismatch."""
+    # (bytes are copied once: torch takes writable arrays only; LayoutDataset reads the zip entry straight into an array instead)
+    arr = np.frombuffer(data, np.uint8).copy() if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+    from .. import _lib
+    lib = _lib.load()                                    # (not core.lib(): that registers a GPU workspace, and this runs in DataLoader workers)
+    w, h, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    k, r = ctypes.c_int64(0), ctypes.c_int64(0)
+    src = arr.ctypes.data_as(ctypes.c_void_p)
+
+    def call(seg, rows):
+        rc = lib.ldetr_png_scan(src, arr.size, ctypes.byref(w), ctypes.byref(h), ctypes.byref(c), seg.ctypes.data_as(ctypes.c_void_p) if seg is not None else None,
+                                len(seg) if seg is not None else 0, ctypes.byref(k), rows.ctypes.data_as(ctypes.c_void_p) if rows is not None else None,
+                                len(rows) if rows is not None else 0, ctypes.byref(r))
+        if rc == PNG_MALFORMED:
+            raise ValueError(lib.ldetr_last_error().decode('utf-8', 'replace'))
+        if rc != PNG_NOT_ELIGIBLE:
+            _lib.check(rc, 'png_scan')
+        return rc
+    if call(None, None) == PNG_NOT_ELIGIBLE:
+        return None
+    seg, rows = np.zeros((k.value, 3), np.int64), np.zeros(r.value, np.int32)
+    call(seg, rows)
+    if verify:
+        z = _verify_png(arr)
+        payload = b''.join(arr[o:o + n].tobytes() for o, _, n in seg)
+        if len(z) < 4 or zlib.adler32(payload) != struct.unpack('>I', z[-4:])[0]:
+            raise ValueError('scan_png: Adler-32 mismatch in the zlib stream')
+    return RawPage(arr, w.value, h.value, seg, rows)
+
+
+def _png_tables(pages):
+    """Host tables of one `ldetr_png_decode_u8` call: file offsets (each file 16-byte aligned) [n + 1], segments [k, 4], row ranges [j, 3], buffer bytes."""
+    off, segs, jobs, pos = [], [], [], 0
+    for i, p in enumerate(pages):
+        off.append(pos)
+        pos += (int(p.tensor().numel()) + 15) // 16 * 16
+        segs.append(np.concatenate([np.full((len(p.segments), 1), i, np.int64), np.asarray(p.segments, np.int64).reshape(-1, 3)], 1))
+        starts = np.asarray(p.row_starts, np.int32).reshape(-1)
+        jobs.append(np.stack([np.full(len(starts), i, np.int32), starts, np.append(starts[1:], np.int32(p.height))], 1))
+    off.append(pos)                                                        # a multiple of 16: the end of the padded last file
+    return np.asarray(off, np.int64), np.ascontiguousarray(np.concatenate(segs, 0)), np.ascontiguousarray(np.concatenate(jobs, 0).astype(np.int32)), pos
+
+
+def _decode_group(pages, device, phases=3, state=None):
+    """One `ldetr_png_decode_u8` call: RawPages of one size -> uint8 [n, H, W, 3] on `device`.  `state` (tools/bench_page_decode.py) keeps the
+    uploaded buffers between calls that time the two launches apart."""
+    from .. import _lib
+    n, H, W = len(pages), pages[0].height, pages[0].width
+    if state is None or 'files' not in state:
+        off, seg, jobs, nbytes = _png_tables(pages)
+        host = torch.zeros(nbytes, dtype=torch.uint8, pin_memory=all(p.tensor().is_pinned() for p in pages))
+        for i, p in enumerate(pages):
+            t = p.tensor()
+            host[int(off[i]):int(off[i]) + t.numel()] = t
+        tables = torch.from_numpy(np.concatenate([off.view(np.uint8), seg.reshape(-1).view(np.uint8), jobs.reshape(-1).view(np.uint8)]))
+        st = dict(off=off, seg=seg, jobs=jobs, files=host.to(device, non_blocking=True), tables=tables.to(device, non_blocking=True),
+                  scratch=torch.empty((n * H * (1 + 3 * W) + 15) // 16 * 16, dtype=torch.uint8, device=device),
+                  dst=torch.empty((n, H, W, 3), dtype=torch.uint8, device=device))
+        if state is not None:
+            state.update(st)
+    else:
+        st = state
+    core.require_gpu(st['files'])
+    tp = st['tables'].data_ptr()                                          # [file offsets | segments | row ranges], as on the host
+    a = _lib.PngDecodeArgs(struct_bytes=ctypes.sizeof(_lib.PngDecodeArgs), n=n, H=H, W=W, phases=phases, reserved=0,
+                           files=core.ptr(st['files']), files_bytes=st['files'].numel(),
+                           file_off=st['off'].ctypes.data, file_off_dev=tp,
+                           segments=st['seg'].ctypes.data, segments_dev=tp + st['off'].nbytes, n_segments=len(st['seg']),
+                           jobs=st['jobs'].ctypes.data, jobs_dev=tp + st['off'].nbytes + st['seg'].nbytes, n_jobs=len(st['jobs']),
+                           scratch=core.ptr(st['scratch']), scratch_bytes=st['scratch'].numel(), dst=core.ptr(st['dst']))
+    core.check(core.lib().ldetr_png_decode_u8(ctypes.byref(a), core.stream()), 'png_decode_u8')
+    return st['dst']
+
+
+def decode_pages(raw_pages, device):
+    """`RawPage`s -> the decoded pages in GPU memory, bit-identical to np.array(PIL.Image.open(...)): uint8 [n, H, W, 3] when the pages share
+    a size, else a list of [H, W, 3] tensors in the order given.  One `ldetr_png_decode_u8` call (two launches) per distinct page size.
+    There is no CPU path: without a GPU device it raises."""
+    raw_pages = list(raw_pages)
+    if not raw_pages or not all(isinstance(p, RawPage) for p in raw_pages):
+        raise ValueError('decode_pages: expected a non-empty sequence of RawPage')
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f'decode_pages: needs a GPU device (got {device}); layoutdetr_amd has no CPU path')
+    groups = {}
+    for i, p in enumerate(raw_pages):
+        groups.setdefault((p.height, p.width), []).append(i)
+    if len(groups) == 1:
+        return _decode_group(raw_pages, device)
+    out = [None] * len(raw_pages)
+    for idx in groups.values():
+        dec = _decode_group([raw_pages[i] for i in idx], device)
+        for j, i in enumerate(idx):
+            out[i] = dec[j]
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -243,13 +404,18 @@ class Dataset(torch.utils.data.Dataset):
 class LayoutDataset(Dataset):
     """dataset_layoutganpp.py:214-352.  See the module docstring for `mode`."""
 
-    def __init__(self, path, xflip=False, background_size=1024, mode='device', **super_kwargs):
-        if mode not in ('device', 'reference'):
-            raise ValueError("LayoutDataset: mode must be 'device' or 'reference'")
+    def __init__(self, path, xflip=False, background_size=1024, mode=None, verify_png=False, **super_kwargs):
+        if mode is None:
+            mode = default_dataset_mode()
+        if mode not in DATASET_MODES:
+            raise ValueError("LayoutDataset: mode must be 'device', 'raw' or 'reference'")
+        self.verify_png = bool(verify_png)
+        self.route_counts = {'raw': 0, 'decoded': 0}         # mode='raw': items whose page went out as file bytes / was decoded here with Pillow
         self._path = path
         self.background_size = background_size
         self.mode = mode
         self._zipfile = None
+        self._rawfile = None                                 # mode='raw': a second handle on the archive for reading stored entries as they are
         if os.path.splitext(self._path)[1].lower() != '.zip':
             raise IOError('Path must point to a zip')                        # :229
         self._type = 'zip'
@@ -274,15 +440,38 @@ class LayoutDataset(Dataset):
     def _open_file(self, fname):
         return self._get_zipfile().open(fname, 'r')
 
+    def _read_entry(self, fname):
+        """The bytes of one archive entry as a writable uint8 array.  A ZIP_STORED entry (what dataset_tool.py writes) is read straight from the
+        archive file at its data offset: no inflate, and not zipfile's CRC-32 pass over the bytes either (`scan_png(verify=True)` checks the PNG's own
+        checksums); any other entry goes through zipfile."""
+        info = self._get_zipfile().getinfo(fname)
+        if info.compress_type != zipfile.ZIP_STORED or info.flag_bits & 0x1:
+            return np.frombuffer(self._get_zipfile().read(fname), np.uint8).copy()
+        if self._rawfile is None:
+            self._rawfile = open(self._path, 'rb')
+        f = self._rawfile
+        f.seek(info.header_offset)
+        hdr = f.read(30)
+        if len(hdr) != 30 or hdr[:4] != b'PK\x03\x04':
+            raise IOError(f'{self._path}: no local file header for {fname}')
+        n, m = struct.unpack('<HH', hdr[26:30])
+        f.seek(info.header_offset + 30 + n + m)
+        data = np.empty(info.file_size, np.uint8)
+        if f.readinto(data) != data.size:
+            raise IOError(f'{self._path}: {fname}: short read')
+        return data
+
     def close(self):
         try:
             if self._zipfile is not None:
                 self._zipfile.close()
+            if self._rawfile is not None:
+                self._rawfile.close()
         finally:
-            self._zipfile = None
+            self._zipfile = self._rawfile = None
 
     def __getstate__(self):                      # DataLoader workers re-open the archive themselves
-        return dict(super().__getstate__(), _zipfile=None)
+        return dict(super().__getstate__(), _zipfile=None, _rawfile=None)
 
     def _patch_orig_shape(self, raw_idx):
         """[9, 3, H, W] of sample `raw_idx`'s '<base>_0_patch_orig.png' — the reference decodes the whole sample to learn this (:238);
@@ -357,6 +546,19 @@ class LayoutDataset(Dataset):
             out['background'] = page                                                          # uint8 [H, W, 3]; resized + normalised on the GPU
             out['patches'] = np.broadcast_to(np.zeros((), np.float32), (9, 3, 256, 256))      # shape only, never read
             return out
+        if self.mode == 'raw':
+            data = self._read_entry(base + '_background_orig.png')
+            raw = scan_png(data, verify=self.verify_png)
+            if raw is None:                                                                   # not a stored-block 8-bit RGB file: this item takes the 'device' route
+                import PIL.Image
+                page = np.array(PIL.Image.open(io.BytesIO(data.tobytes())))
+                if page.ndim != 3 or page.shape[2] != 3:
+                    raise ValueError(f'{base}_background_orig.png: expected an RGB page (:334)')
+                raw = page
+            self.route_counts['raw' if isinstance(raw, RawPage) else 'decoded'] += 1
+            out['background'] = raw
+            out['patches'] = np.broadcast_to(np.zeros((), np.float32), (9, 3, 256, 256))
+            return out
         import PIL.Image
         lanczos = PIL.Image.LANCZOS                                                           # = the reference's PIL.Image.ANTIALIAS (alias removed in Pillow 10)
         mean = np.reshape(np.array(RGB_MEAN).astype(np.float32), (1, 1, 3))
@@ -409,7 +611,9 @@ class LayoutDataset(Dataset):
         out['name'] = [s['name'] for s in samples]
         out['texts'] = [tuple(s['texts'][j] for s in samples) for j in range(9)]
         pages = [s['background'] for s in samples]
-        if pages[0].dtype == np.uint8:
+        if any(isinstance(p, RawPage) for p in pages):                       # mode='raw': a list, file bytes and (fallback) decoded pages side by side
+            out['background'] = [p if isinstance(p, RawPage) else torch.from_numpy(np.ascontiguousarray(p)) for p in pages]
+        elif pages[0].dtype == np.uint8:
             same = all(p.shape == pages[0].shape for p in pages)
             out['background'] = torch.from_numpy(np.stack(pages, 0)) if same else [torch.from_numpy(np.ascontiguousarray(p)) for p in pages]
         else:
@@ -429,6 +633,7 @@ def batch_backgrounds_to_device(background, background_size, device, page_filter
     """'background' of a collated batch -> float32 [B, 3, S, S] on `device`.  uint8 pages (mode='device': one [B, H, W, 3] tensor, or a
     list when page sizes differ) are uploaded as bytes and resized + normalised by `background_to_tensor`, one call per distinct page
     size; float input (mode='reference' / other datasets) is what the reference already hands over (training_loop.py:264).
+    `RawPage`s in the list (mode='raw') are uploaded as file bytes and decoded on the device first (`decode_pages`), then treated like the rest.
     page_filter ('blur' / 'edge') filters the uint8 pages before the resize; float backgrounds are already resized, so a filter on them raises."""
     if page_filter is not None and page_filter not in PAGE_FILTER_KINDS:
         raise ValueError(f'batch_backgrounds_to_device: page_filter must be None or one of {sorted(PAGE_FILTER_KINDS)} (got {page_filter!r})')
@@ -438,13 +643,22 @@ def batch_backgrounds_to_device(background, background_size, device, page_filter
                 raise ValueError('batch_backgrounds_to_device: page_filter needs the decoded uint8 pages (dataset mode=\'device\'), not float backgrounds')
             return background.to(device).float()
         return background_to_tensor(background.to(device, non_blocking=True), background_size, page_filter=page_filter)
+    raw = [i for i, p in enumerate(background) if isinstance(p, RawPage)]
+    if raw:                                                                  # mode='raw': the file bytes go up, the pages are decoded there
+        dec = decode_pages([background[i] for i in raw], device)
+        if len(raw) == len(background) and torch.is_tensor(dec):
+            return background_to_tensor(dec, background_size, page_filter=page_filter)
+        background = list(background)
+        for j, i in enumerate(raw):
+            background[i] = dec[j]
     groups = {}
     for i, p in enumerate(background):
         groups.setdefault(tuple(p.shape), []).append(i)
     out = torch.empty((len(background), 3, background_size, background_size), dtype=torch.float32, device=device)
     for idx in groups.values():
-        out[torch.tensor(idx, device=device)] = background_to_tensor(torch.stack([background[i] for i in idx]).to(device, non_blocking=True), background_size,
-                                                                         page_filter=page_filter)
+        pages = [background[i] for i in idx]
+        pages = torch.stack([p.to(device, non_blocking=True) for p in pages]) if raw else torch.stack(pages).to(device, non_blocking=True)
+        out[torch.tensor(idx, device=device)] = background_to_tensor(pages, background_size, page_filter=page_filter)
     return out
 
 

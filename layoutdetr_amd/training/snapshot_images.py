@@ -72,16 +72,25 @@ class SnapshotGrid(object):
     host copies of the masks and labels (the raster entry reads those on the host)."""
 
     def __init__(self, name, dataset, G, batch_size, batch_gpu, device, colors, random_seed=0, kinds=DEFAULT_KINDS, image_canvas=IMAGE_CANVAS):
+        from .dataset_layoutganpp import RawPage, decode_pages
         from .training_loop import assemble_batch
         self.name, self.device, self.colors = name, device, [tuple(int(v) for v in c) for c in colors]
         self.kinds, self.image_canvas = parse_kinds(kinds), int(image_canvas)
         self.indices = grid_indices(len(dataset), batch_size, random_seed)
         items = [dataset[i] for i in self.indices]
-        collate = dataset.collate if (getattr(dataset, 'mode', None) == 'device' and hasattr(dataset, 'collate')) else torch.utils.data.default_collate
+        collate = dataset.collate if (getattr(dataset, 'mode', None) in ('device', 'raw') and hasattr(dataset, 'collate')) else torch.utils.data.default_collate
         self.page_wh = [(int(s['W_page']), int(s['H_page'])) for s, _ in items]
         pages = [s['background'] for s, _ in items]
         self.pages = self.pages_wh = None
-        if all(isinstance(p, np.ndarray) and p.dtype == np.uint8 and p.ndim == 3 for p in pages):
+        raw = [i for i, p in enumerate(pages) if isinstance(p, RawPage)]
+        if raw:                                                            # mode='raw': the same uint8 pages, decoded on the device
+            dec = decode_pages([pages[i] for i in raw], device)
+            pages = list(pages)
+            for j, i in enumerate(raw):
+                pages[i] = dec[j]
+            self.pages = render.PageSet([p if torch.is_tensor(p) else torch.from_numpy(np.ascontiguousarray(p)).to(device) for p in pages])
+            self.pages_wh = [(int(p.shape[1]), int(p.shape[0])) for p in pages]
+        elif all(isinstance(p, np.ndarray) and p.dtype == np.uint8 and p.ndim == 3 for p in pages):
             self.pages = render.PageSet([torch.from_numpy(np.ascontiguousarray(p)).to(device) for p in pages])
             self.pages_wh = [(int(p.shape[1]), int(p.shape[0])) for p in pages]      # the decoded page's own size
         self.patches = None
