@@ -208,7 +208,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(PoolParams p) {
         int ox = (int)(t % p.OW); t /= p.OW;
         int oy = (int)(t % p.OH); int n = (int)(t / p.OH);
         float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        uchar4 mi = make_uchar4(0, 0, 0, 0);
+        // the index starts at the window's first in-image tap (row 1 / column 1 of a border window), as F.max_pool2d's does: a window whose
+        // in-image elements are all -inf then routes its gradient there and not to a tap outside the image
+        const unsigned char k0 = (unsigned char)((oy == 0 ? 3 : 0) + (ox == 0 ? 1 : 0));
+        uchar4 mi = make_uchar4(k0, k0, k0, k0);
 #pragma unroll
         for (int kh = 0; kh < 3; kh++) {
             int y = oy * 2 - 1 + kh;
