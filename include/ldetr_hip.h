@@ -385,7 +385,8 @@ int ldetr_ema_lerp_f32(float* p_ema, const float* p, int64_t n, float beta, void
  * prediction scores, training/med.py:911-916; ignore_index marks padded tokens).  fwd: one pass over logits [rows, V] (row pitch
  * ld): row_lse[i] = logsumexp, *loss_sum += sum_i loss_i, *count += #(targets != ignore_index) (both zeroed by the caller; the mean
  * is loss_sum / count).  bwd: dlogits[i, c] = (softmax - (1 - eps) onehot - eps / V) * (*grad_out) / (*count), zero rows for
- * ignored targets; dlogits may alias logits. */
+ * ignored targets; dlogits may alias logits.  Logits may be -inf (masked vocabulary entries): with label_smoothing = 0 the row's loss and
+ * gradient are finite as long as the target's logit is. */
 int ldetr_softmax_xent_fwd_f32(const float* logits, int64_t ld, const int64_t* targets, float* row_lse, float* loss_sum, float* count,
                                int64_t rows, int V, int64_t ignore_index, float label_smoothing, void* stream);
 int ldetr_softmax_xent_bwd_f32(const float* logits, int64_t ld, const int64_t* targets, const float* row_lse, const float* count,

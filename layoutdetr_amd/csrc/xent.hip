@@ -28,6 +28,11 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
     m = mn;
 }
 
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    return a * b + c;      // two roundings
+}
+
 // Rows are dealt round-robin to the blocks and each block adds its share of the loss once: one atomic per ROW made 2 x rows
 // same-address device-scope atomics (~0.1 us each on this multi-die part) the longest thing in the kernel.
 __global__ __launch_bounds__(256) void xent_fwd_kernel(XentParams p) {
@@ -43,14 +48,19 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(XentParams p) {
             const float4 v = reinterpret_cast<const float4*>(x)[i];
             const float mv = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
             const float mn = fmaxf(m, mv);
-            s = s * __expf(m - mn) + __expf(v.x - mn) + __expf(v.y - mn) + __expf(v.z - mn) + __expf(v.w - mn);
+            // everything seen so far -inf (masked logits): m - mn and v - mn are -inf - (-inf) = NaN; s stays 0 as in online_merge.  (m alone -inf:
+            // __expf(-inf) = 0 times s = 0, no guard needed.)  The roundings are spelled out, fused here and product-then-sum in the tail loop, as
+            // both loops were compiled before the guard: rows of finite logits keep their bits (tests/golden/xent_guard.npz).
+            const float sn = __fmaf_rn(s, __expf(m - mn), __expf(v.x - mn)) + __expf(v.y - mn) + __expf(v.z - mn) + __expf(v.w - mn);
+            s = mn == -INFINITY ? 0.f : sn;
             m = mn;
             sx += (v.x + v.y) + (v.z + v.w);
         }
         for (int i = (V4 << 2) + threadIdx.x; i < p.V; i += 256) {
             const float v = x[i];
             const float mn = fmaxf(m, v);
-            s = s * __expf(m - mn) + __expf(v - mn);
+            const float sn = mul_then_add(s, __expf(m - mn), __expf(v - mn));
+            s = mn == -INFINITY ? 0.f : sn;
             m = mn; sx += v;
         }
     }
@@ -72,7 +82,8 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(XentParams p) {
         if (valid) {
             const float lse = m + logf(s);
             p.row_lse[row] = lse;
-            const float li = lse - (1.f - p.eps) * x[t] - p.eps * (sx / (float)p.V);
+            float li = lse - (1.f - p.eps) * x[t];
+            if (p.eps > 0.f) li -= p.eps * (sx / (float)p.V);   // no smoothing term at eps = 0 (as F.cross_entropy): 0 * mean is NaN for a row with a -inf logit
             block_loss += li; block_count += 1.f;
         } else {
             p.row_lse[row] = 0.f;
