@@ -96,10 +96,15 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnParams pa, LnParams pb, i
 
 // Backward: dz = rstd * (g - mean(g) - xhat * mean(g*xhat)), g = dy*gamma.
 // dx = dz; dr = dz * dropmask (regenerated).  dgamma/dbeta: per-wave register partials over a
-// grid-stride row loop, LDS combine across the 4 waves, one atomicAdd per block per column.
-template <int NV>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(LnParams pa, LnParams pb, int nb0) {
-    __shared__ float red[2][4][256 * NV];
+// grid-stride row loop, LDS combine across the block's waves, one atomicAdd per block per column.
+// WAVES = rows per block pass.  The atomics of all blocks queue on the 16 cache lines of dgamma / dbeta (gx * 2 * D of them: 262 k at 2048 rows in
+// blocks of 4 rows, 12 of the launch's 16 us), so from 256 rows on a block is 16 waves: a quarter of the atomics behind the same row loop
+// (1024 rows 9.4 -> 5.7 us, 2048 rows 15.9 -> 7.5 us; below 256 rows the small blocks are 0.1-0.3 us faster and stay).  Doing the block sums in
+// two stages inside the launch instead (partials through the workspace, the last-arriving block adds them in order: bit-reproducible) was measured
+// and dropped: its store -> counter -> load chain costs 2.7 us per launch, more than the atomics of a short stack.
+template <int NV, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void ln_bwd_kernel(LnParams pa, LnParams pb, int nb0) {
+    __shared__ float red[2][WAVES][256 * NV];
     const bool second = (int)blockIdx.x >= nb0;
     const LnParams& p = second ? pb : pa;
     const int bx = second ? (int)blockIdx.x - nb0 : (int)blockIdx.x, gx = second ? (int)gridDim.x - nb0 : nb0;
@@ -110,7 +115,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnParams pa, LnParams pb, i
     float4 ag[NV], ab[NV];
 #pragma unroll
     for (int i = 0; i < NV; i++) { ag[i] = make_float4(0.f, 0.f, 0.f, 0.f); ab[i] = ag[i]; }
-    for (long row = (long)bx * 4 + wave; row < p.rows; row += (long)gx * 4) {
+    for (long row = (long)bx * WAVES + wave; row < p.rows; row += (long)gx * WAVES) {
         const float mean = p.mean[row], rstd = p.rstd[row];
         float4 xh[NV], g[NV];
         float s1 = 0.f, s2 = 0.f;
@@ -175,11 +180,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnParams pa, LnParams pb, i
         red[1][wave][c + 0] = ab[i].x; red[1][wave][c + 1] = ab[i].y; red[1][wave][c + 2] = ab[i].z; red[1][wave][c + 3] = ab[i].w;
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < p.D; c += 256) {
-        float g = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
-        float b = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
-        atomicAdd(p.dgamma + c, g);
-        atomicAdd(p.dbeta + c, b);
+    for (int c = threadIdx.x; c < 2 * p.D; c += WAVES * 64) {      // column c of [dgamma | dbeta]
+        const int k = c >= p.D, cc = c - k * p.D;
+        float sum = red[k][0][cc];
+#pragma unroll
+        for (int w = 1; w < WAVES; w++) sum += red[k][w][cc];
+        atomicAdd((k ? p.dbeta : p.dgamma) + cc, sum);
     }
 }
 
@@ -231,15 +237,20 @@ extern "C" int ldetr_layernorm_bwd_group_f32(const ldetr_ln_args* a, int n, void
     for (int i = 0; i < n; i++)
         if (int rc = ln_check_bwd(p[i])) return rc;
     LDETR_CHECK(n == 1 || p[0].D == p[1].D, "layernorm_bwd_group: both problems must have the same D");
-    auto blocks = [](long rows) { long g = (rows + 3) / 4; return (int)(g > 512 ? 512 : g); };
+    // blocks of 16 rows where a problem has enough rows for the atomics to matter (ln_bwd_kernel); a sweep of the capped grid is 2048 rows either way
+    static const long wide_rows = knob("LN_BWD_WIDE_ROWS", 256);
+    const int nv = (p[0].D + 255) / 256;
+    const int waves = nv == 1 && std::max<int64_t>(p[0].rows, n == 2 ? p[1].rows : 0) >= wide_rows ? 16 : 4;
+    auto blocks = [waves](long rows) { long g = (rows + waves - 1) / waves; return (int)(g > 2048 / waves ? 2048 / waves : g); };
     const int nb0 = blocks(p[0].rows), nb1 = n == 2 ? blocks(p[1].rows) : 0;
     if (nb0 + nb1 == 0) return LDETR_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int nv = (p[0].D + 255) / 256, grid = nb0 + nb1;
-    if (nv == 1) hipLaunchKernelGGL(ln_bwd_kernel<1>, grid, 256, 0, st, p[0], p[1], nb0);
-    else if (nv == 2) hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, 256, 0, st, p[0], p[1], nb0);
-    else if (nv == 3) hipLaunchKernelGGL(ln_bwd_kernel<3>, grid, 256, 0, st, p[0], p[1], nb0);
-    else hipLaunchKernelGGL(ln_bwd_kernel<4>, grid, 256, 0, st, p[0], p[1], nb0);
+    const int grid = nb0 + nb1;
+    if (waves == 16) hipLaunchKernelGGL((ln_bwd_kernel<1, 16>), grid, 1024, 0, st, p[0], p[1], nb0);
+    else if (nv == 1) hipLaunchKernelGGL((ln_bwd_kernel<1, 4>), grid, 256, 0, st, p[0], p[1], nb0);
+    else if (nv == 2) hipLaunchKernelGGL((ln_bwd_kernel<2, 4>), grid, 256, 0, st, p[0], p[1], nb0);
+    else if (nv == 3) hipLaunchKernelGGL((ln_bwd_kernel<3, 4>), grid, 256, 0, st, p[0], p[1], nb0);
+    else hipLaunchKernelGGL((ln_bwd_kernel<4, 4>), grid, 256, 0, st, p[0], p[1], nb0);
     return check_launch("layernorm_bwd");
 }
 

@@ -3,7 +3,7 @@
 // all_reduce, /num_gpus, nan_to_num, split + per-tensor Adam) and the G_ema lerp at :320-328.
 // With all parameters of a module laid out in one contiguous fp32 buffer the gradient exchange
 // needs no pack/unpack copies and the optimiser is a single streaming launch:
-//   Adam: reads p, g, m, v and writes p, m, v = 28 B/parameter;  EMA: 12 B/parameter.
+//   Adam: reads p, g, m, v and writes p, m, v = 28 B/parameter (24 at beta1 == 0: m is not read);  EMA: 12 B/parameter.
 #include "ldetr_common.hpp"
 #include "../../include/ldetr_hip.h"
 
@@ -37,12 +37,16 @@ struct AdamParams {
     float* pe; float ema_beta;      // optional: p_ema = lerp(p_new, p_ema, beta) in the same pass (G_ema, training_loop.py:320-328)
 };
 
+// B1Z: beta1 == 0 (the training setting, betas = (0, 0.99)): m_new = g whatever m held and the bias correction 1 - beta1^step is 1, so the caller
+// does not load m at all (`m` is write-only here) -- 24 instead of 28 B/parameter.  For a finite m the general formula gives the same bits.
+template <bool B1Z>
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamParams& a) {
     if (a.fuse_sanitize) g = sanitize(g, a.gscale, a.nanv, a.posinf, a.neginf);
-    m = a.b1 * m + (1.f - a.b1) * g;
+    if constexpr (B1Z) m = g;
+    else m = a.b1 * m + (1.f - a.b1) * g;
     v = a.b2 * v + (1.f - a.b2) * g * g;
     float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p -= (a.lr / a.bc1) * (m / denom);
+    p -= (B1Z ? a.lr : a.lr / a.bc1) * (m / denom);
 }
 
 // Block -> address mapping (round 6, tools/probes/stream_probe.hip at D's 90 M parameters = 1.44 GB of p / g / m / v, far beyond the 256 MB Infinity Cache): a block owns
@@ -50,7 +54,7 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
 // XCD-contiguous eighths (each XCD streaming its own region: worse, not better), 4.9 .. 5.4 for 64 KB .. 1 MB chunks; a plain copy on the same box reaches 5.64 TB/s.
 constexpr long STREAM_CHUNK4 = 1024;     // float4 per chunk
 
-template <bool EMA>      // (as a run-time branch on a.pe the plain step lost 7 % of its rate: 5.19 vs 5.58 TB/s)
+template <bool EMA, bool B1Z>      // (as a run-time branch on a.pe the plain step lost 7 % of its rate: 5.19 vs 5.58 TB/s; beta1 == 0 is compile-time for the same reason)
 __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
     const long n4 = a.n >> 2;
     const long stride = (long)gridDim.x * blockDim.x;
@@ -61,12 +65,13 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
         // stream does not evict the parameters, which the next phase's first kernels read
         f32x4 pv = reinterpret_cast<f32x4*>(a.p)[i];
         f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.g) + i);
-        f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(a.m) + i);
+        f32x4 mv = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (!B1Z) mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(a.m) + i);
         f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(a.v) + i);
         float4 p = make_float4(pv[0], pv[1], pv[2], pv[3]), g = make_float4(gv[0], gv[1], gv[2], gv[3]);
         float4 m = make_float4(mv[0], mv[1], mv[2], mv[3]), v = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        adam_elem(p.x, g.x, m.x, v.x, a); adam_elem(p.y, g.y, m.y, v.y, a);
-        adam_elem(p.z, g.z, m.z, v.z, a); adam_elem(p.w, g.w, m.w, v.w, a);
+        adam_elem<B1Z>(p.x, g.x, m.x, v.x, a); adam_elem<B1Z>(p.y, g.y, m.y, v.y, a);
+        adam_elem<B1Z>(p.z, g.z, m.z, v.z, a); adam_elem<B1Z>(p.w, g.w, m.w, v.w, a);
         reinterpret_cast<float4*>(a.p)[i] = p;
         __builtin_nontemporal_store(f32x4{m.x, m.y, m.z, m.w}, reinterpret_cast<f32x4*>(a.m) + i);
         __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(a.v) + i);
@@ -78,7 +83,10 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
       }
     }
     for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
-        adam_elem(a.p[i], a.g[i], a.m[i], a.v[i], a);
+        float m = 0.f;
+        if constexpr (!B1Z) m = a.m[i];
+        adam_elem<B1Z>(a.p[i], a.g[i], m, a.v[i], a);
+        a.m[i] = m;
         if constexpr (EMA) a.pe[i] = a.p[i] + a.ema_beta * (a.pe[i] - a.p[i]);
     }
 }
@@ -147,8 +155,15 @@ extern "C" int ldetr_adam_ema_step_f32(float* p, const float* g, float* m, float
     a.bc1 = (float)bc1; a.bc2_sqrt = (float)sqrt(bc2);
     a.fuse_sanitize = fuse_sanitize; a.gscale = gscale; a.nanv = nan_value; a.posinf = posinf; a.neginf = neginf;
     a.pe = p_ema; a.ema_beta = ema_beta;
-    if (p_ema) hipLaunchKernelGGL(adam_kernel<true>, stream_grid(n), 256, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(adam_kernel<false>, stream_grid(n), 256, 0, (hipStream_t)stream, a);
+    const int grid = stream_grid(n);
+    hipStream_t st = (hipStream_t)stream;
+    if (beta1 == 0.0f) {
+        if (p_ema) hipLaunchKernelGGL((adam_kernel<true, true>), grid, 256, 0, st, a);
+        else hipLaunchKernelGGL((adam_kernel<false, true>), grid, 256, 0, st, a);
+    } else {
+        if (p_ema) hipLaunchKernelGGL((adam_kernel<true, false>), grid, 256, 0, st, a);
+        else hipLaunchKernelGGL((adam_kernel<false, false>), grid, 256, 0, st, a);
+    }
     return check_launch("adam_step");
 }
 

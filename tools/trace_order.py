@@ -1,6 +1,6 @@
 """Development aid: the ORDERED kernel sequence of one replayed iteration (what follows what on the phase's in-order queue).
 python tools/trace_order.py <kernel_trace.csv> [out.txt]   (csv from `rocprofv3 --kernel-trace --output-format csv`)
-One line per launch of the last complete iteration (delimited by adam_kernel<true> = G's optimiser step with the EMA ride-along):
+One line per launch of the last complete iteration (delimited by adam_kernel<true, ...> = G's optimiser step with the EMA ride-along):
 start offset [us], duration [us], gap to the previous kernel's end [us], short kernel name.  A run-length summary follows."""
 import collections
 import csv
@@ -28,7 +28,7 @@ def main():
         for r in csv.DictReader(f):
             rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name']))
     rows.sort()
-    marks = [i for i, r in enumerate(rows) if 'adam_kernel<true>' in r[2]]
+    marks = [i for i, r in enumerate(rows) if 'adam_kernel<true' in r[2]]
     lo, hi = marks[-2] + 1, marks[-1] + 1
     seg = rows[lo:hi]
     out = open(sys.argv[2], 'w') if len(sys.argv) > 2 else sys.stdout
