@@ -9,6 +9,11 @@
 // Subgradient conventions are autograd's: maximum / minimum split a tie half-half, where() passes the gradient of the taken
 // branch only, abs' = sign, min(dim) routes to the first arg-min, nan_to_num blocks the gradient of the entries it replaced, and
 // compute_alignment keeps its quirk of comparing valid boxes against padded ones too (the mask is applied to rows only).
+// Two deliberate deviations from the reference, both where it returns NaN and the step would be zeroed behind the gradient sanitiser
+// (pinned by tests/test_loss_tail_gpu.py):
+//   1. a sample without a valid box: all four shares and the whole gradient block are 0 (the reference's overlap and alignment are 0 / 0 = NaN);
+//   2. a valid box of zero area (w == 0 or h == 0): its overlap gradient row is 0 (the reference's row is NaN: 0 * inf behind nan_to_num, which
+//      blocks the replaced entry's gradient but not the 1 / 0 of the division under it); its value and every other row agree.
 //   losses [4][B]: per-sample shares, so that  mse = losses[0].sum(), gIoU = losses[1].sum(), overlap = losses[2] ([B]),
 //                  alignment = losses[3] ([B]).   grads [4][B][N][4] = d losses[t][b] / d bbox[b].
 #include <algorithm>
@@ -58,7 +63,7 @@ __global__ __launch_bounds__(64) void layout_losses_kernel(LayoutLossParams p) {
     __syncthreads();
     int nb = 0;
     for (int j = 0; j < N; j++) nb += sv[j];
-    const float inv_nb = 1.f / (float)nb;     // a sample without valid boxes gives 0 / 0 in the reference as well
+    const float inv_nb = 1.f / (float)nb;     // nb == 0: inf, never used (no lane is valid): the sample's outputs stay 0 where the reference has 0 / 0 = NaN (deviation 1)
 
     float l_mse = 0.f, l_giou = 0.f, l_ovl = 0.f, l_aln = 0.f;
     float g_mse[4] = {0.f, 0.f, 0.f, 0.f}, g_giou[4] = {0.f, 0.f, 0.f, 0.f}, g_ovl[4] = {0.f, 0.f, 0.f, 0.f}, g_aln[4] = {0.f, 0.f, 0.f, 0.f};
