@@ -37,6 +37,8 @@
  *   ldetr_png_scan, ldetr_png_decode_u8
  *                                 PIL.Image.open + np.array of a page PNG written with compress_level=0: dataset_tool.py:325-363,
  *                                 training/dataset_layoutganpp.py:329-340
+ *   ldetr_png_encode_bound, ldetr_png_encode_u8
+ *                                 the PNG encoder behind the snapshot grids' save: util.py:141, 231, 325
  *   ldetr_resample_coeffs_filter, ldetr_layout_raster_cell_size, ldetr_layout_raster_u8
  *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
  *   ldetr_patch_resize_u8, ldetr_image_raster_u8
@@ -581,6 +583,34 @@ typedef struct ldetr_png_decode_args {
 int ldetr_png_scan(const uint8_t* file, int64_t file_bytes, int* width, int* height, int* channels, int64_t* segments, int64_t segments_capacity,
                    int64_t* segments_count, int32_t* row_starts, int64_t row_starts_capacity, int64_t* row_starts_count);
 int ldetr_png_decode_u8(const ldetr_png_decode_args* a, void* stream);
+
+/* A snapshot grid encoded as a PNG file on the device (csrc/png_encode.hip): uint8 [H][W][3] in GPU memory -> the bytes of an
+ * 8-bit RGB PNG in GPU memory, what `PIL.Image.fromarray(grid).save(path)` of util.py:141 and util.py:231,325 produces on the host.  Row filters
+ * (minimum sum of absolute residuals, ties to the lowest type), deflate (the filtered stream cut into segments of 64 KiB, each compressed on its
+ * own by one workgroup into the smallest of a stored, a fixed-Huffman and a dynamic-Huffman block and ended byte-aligned, each its own IDAT chunk),
+ * the Adler-32 and every chunk's CRC-32 are computed on the device, in three launches with no host synchronisation between them.
+ * ldetr_png_encode_bound (HOST, no GPU work): out_bytes = the largest file blocks = 0 / 1 can give (every segment stored), workspace_bytes = what
+ * `workspace` must hold.  1 <= W, H <= 16384, else LDETR_ERR_ARG.
+ * ldetr_png_encode_u8: validates on the host (sizes, modes, out_capacity >= the bound, workspace) and returns LDETR_ERR_ARG without a launch
+ * otherwise.  *total_bytes (device) receives the file length; with blocks = 2 / 3 (a forced block type, which can exceed the stored form) a file
+ * that does not fit out_capacity is cut at the capacity and *total_bytes is minus the length it needed. */
+typedef struct ldetr_png_encode_args {
+    int struct_bytes;             /* sizeof(ldetr_png_encode_args) as the caller sees it */
+    int H, W;
+    int blocks;                   /* 0 the smallest per segment, 1 stored, 2 fixed Huffman, 3 dynamic Huffman */
+    int filter;                   /* -1 chosen per row, 0 .. 4 that type on every row */
+    int reserved;
+    const uint8_t* src;           /* device [H][W][3], contiguous */
+    uint8_t* out;                 /* device: the file */
+    int64_t out_capacity;
+    int64_t* total_bytes;         /* device: one int64 */
+    uint8_t* workspace;           /* device, 16-byte aligned */
+    int64_t workspace_bytes;
+    int64_t* seg_table;           /* optional device [seg_table_rows][4] = (first byte, end byte of the filtered stream, block type 0 / 1 / 2, chunk bytes) */
+    int64_t seg_table_rows;       /* >= the number of segments: ceil(H (1 + 3 W) / 65536) */
+} ldetr_png_encode_args;
+int ldetr_png_encode_bound(int H, int W, int64_t* out_bytes, int64_t* workspace_bytes);
+int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream);
 
 /* Batched linear-sum-assignment (Hungarian / shortest augmenting path) on device.
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;

@@ -110,6 +110,13 @@ class PngDecodeArgs(Structure):
                 ('scratch', c_void_p), ('scratch_bytes', c_int64), ('dst', c_void_p)]
 
 
+class PngEncodeArgs(Structure):
+    """ldetr_png_encode_args."""
+    _fields_ = [('struct_bytes', c_int), ('H', c_int), ('W', c_int), ('blocks', c_int), ('filter', c_int), ('reserved', c_int),
+                ('src', c_void_p), ('out', c_void_p), ('out_capacity', c_int64), ('total_bytes', c_void_p),
+                ('workspace', c_void_p), ('workspace_bytes', c_int64), ('seg_table', c_void_p), ('seg_table_rows', c_int64)]
+
+
 _P = c_void_p
 _I = c_int
 _L = c_int64
@@ -202,6 +209,8 @@ SIGNATURES = {
     'ldetr_page_filter_u8': [_P, _P, _L, _I, _I, _I, _F, _P],
     'ldetr_png_scan': [_P, _L, _P, _P, _P, _P, _L, _P, _P, _L, _P],
     'ldetr_png_decode_u8': [_P, _P],
+    'ldetr_png_encode_bound': [_I, _I, _P, _P],
+    'ldetr_png_encode_u8': [_P, _P],
 }
 
 _lib = None

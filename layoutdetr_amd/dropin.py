@@ -165,20 +165,27 @@ def install_plugins():
     return custom_ops._cached_plugins
 
 
+SNAPSHOT_PNG_ENV = 'LDETR_SNAPSHOT_PNG'       # read by render.save_png where it is not told an encoder (render.PNG_ENV)
 DATASET_MODE_ENV = 'LDETR_DATASET_MODE'       # read by training/dataset_layoutganpp.py where a LayoutDataset is built without an explicit mode
 
 
 def parse_options(argv, environ):
     """The options in front of the script: each sets the environment variable the training code reads; returns what is left of argv.
     --image-snapshot-kinds: which snapshot kinds training_loop writes (training/snapshot_images.py);
-    --dataset-mode: 'device' (Pillow decodes the page on the host) or 'raw' (the page's PNG bytes go to the GPU and are decoded there)."""
+    --dataset-mode: 'device' (Pillow decodes the page on the host) or 'raw' (the page's PNG bytes go to the GPU and are decoded there);
+    --snapshot-png: 'pillow' (the snapshot grid is copied to the host and Pillow encodes it) or 'device' (render.encode_png: the GPU encodes, only the
+    file's bytes are copied)."""
     argv = list(argv)
-    while argv and (argv[0].startswith('--image-snapshot-kinds') or argv[0].startswith('--dataset-mode')):
+    while argv and (argv[0].startswith('--image-snapshot-kinds') or argv[0].startswith('--dataset-mode') or argv[0].startswith('--snapshot-png')):
         opt = argv.pop(0)
         value = opt.split('=', 1)[1] if '=' in opt else (argv.pop(0) if argv else '')
         if opt.startswith('--image-snapshot-kinds'):
             from .training.snapshot_images import KINDS_ENV, parse_kinds
             environ[KINDS_ENV] = ','.join(parse_kinds(value))
+        elif opt.startswith('--snapshot-png'):
+            if value not in ('pillow', 'device'):
+                raise SystemExit(f"--snapshot-png: 'pillow' or 'device' (got {value!r})")
+            environ[SNAPSHOT_PNG_ENV] = value
         else:
             if value not in ('device', 'raw'):
                 raise SystemExit(f"--dataset-mode: 'device' or 'raw' (got {value!r})")
@@ -190,7 +197,7 @@ def main(argv):
     import os
     argv = parse_options(argv, os.environ)
     if not argv:
-        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] [--dataset-mode=device|raw] <script.py> [script args...]')
+        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] [--dataset-mode=device|raw] [--snapshot-png=pillow|device] <script.py> [script args...]')
     sys.path.insert(0, os.path.dirname(os.path.abspath(argv[0])))
     for pkg in ('training', 'torch_utils', 'torch_utils.ops'):     # import the reference's packages first so aliases attach to them
         try:

@@ -2,7 +2,8 @@
 
 The reference builds every grid cell in Python: `boxes[i][mask]` on device tensors, one `ImageDraw.rectangle` per element on a page-sized
 canvas, a PIL resize, `ToTensor`, `make_grid`, `save_image`.  `layout_grid` does all of it in ONE launch (csrc/layout_raster.hip) and returns
-the uint8 grid the reference's PNG holds, bit for bit (the rule is DESIGN.md §13); `save_png` is one device-to-host copy and the PNG encoder.
+the uint8 grid the reference's PNG holds, bit for bit (the rule is DESIGN.md §13); `save_png` is one device-to-host copy and the PNG encoder, or, on
+request, `encode_png`: the PNG file built on the device (csrc/png_encode.hip) and only its bytes copied.
 There is no CPU fallback: without the HIP library or a GPU tensor it raises.
 """
 import ctypes
@@ -170,11 +171,94 @@ def layout_grid(bbox, valid, labels, colors, page_wh, pages=None, page_index=Non
     return out
 
 
-def save_png(grid, path):
-    """Write a uint8 [H, W, 3] grid as a PNG: one device-to-host copy, then PIL encodes."""
-    import PIL.Image
+PNG_ENCODE_SEGMENT = 65536   # csrc/png_encode.hip PE_SEG: bytes of filtered scanline stream per deflate segment (one workgroup, one IDAT chunk)
+PNG_ENCODE_SLOT = 2 * PNG_ENCODE_SEGMENT + 512   # PE_SLOT: the most a segment's deflate bytes take under a forced block type
+PNG_ENV = 'LDETR_SNAPSHOT_PNG'                   # which encoder save_png uses when it is not told: 'pillow' (default) or 'device'
+_BLOCKS = {'auto': 0, 'stored': 1, 'fixed': 2, 'dynamic': 3}
+BLOCK_NAMES = ('stored', 'fixed', 'dynamic')     # block type column of the segment table
+
+
+def _check_grid_size(H, W):
+    if not (1 <= int(W) <= MAX_RESIZE and 1 <= int(H) <= MAX_RESIZE):
+        raise ValueError(f'png encode: a {W} x {H} grid is outside [1, {MAX_RESIZE}] x [1, {MAX_RESIZE}]')
+
+
+def png_encode_bound(H, W):
+    """(file bytes, workspace bytes): the largest file encode_png(blocks='auto' | 'stored') returns for an H x W grid (every segment stored) and the
+    device workspace one call takes (ldetr_png_encode_bound; host arithmetic only)."""
+    _check_grid_size(H, W)
+    out, ws = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().ldetr_png_encode_bound(int(H), int(W), ctypes.byref(out), ctypes.byref(ws)), 'png_encode_bound')
+    return out.value, ws.value
+
+
+def png_encode_segments(H, W):
+    """[(first byte, end byte)]: how the filtered scanline stream of H (1 + 3 W) bytes is cut into deflate segments; no back-reference crosses a
+    seam, and each segment is one IDAT chunk."""
+    _check_grid_size(H, W)
+    total = int(H) * (1 + 3 * int(W))
+    return [(a, min(a + PNG_ENCODE_SEGMENT, total)) for a in range(0, total, PNG_ENCODE_SEGMENT)]
+
+
+def encode_png(grid, blocks='auto', filter='auto', return_stats=False):
+    """A uint8 [H, W, 3] grid in GPU memory -> the bytes of its PNG file as a host uint8 tensor, encoded on the device (csrc/png_encode.hip, DESIGN.md
+    §17): three launches, then one 8-byte copy (the length) and one copy of exactly that many bytes.  blocks: 'auto' takes the smallest of a stored,
+    a fixed-Huffman and a dynamic-Huffman block per 64 KiB segment; 'stored' / 'fixed' / 'dynamic' force one type ('stored' gives a file
+    dataset_layoutganpp.scan_png finds eligible).  filter: 'auto' picks per row by the minimum sum of absolute residuals, 0..4 force a type.
+    return_stats=True: (bytes, stats) with stats['segments'] an int64 [n, 4] array of (first byte, end byte, block type 0 / 1 / 2, chunk bytes).
+    There is no CPU path: a CPU tensor raises."""
+    core.require_gpu(grid)
+    if grid.dtype != torch.uint8 or grid.ndim != 3 or grid.shape[2] != 3:
+        raise ValueError('encode_png: expected a uint8 [H, W, 3] grid')
+    if blocks not in _BLOCKS:
+        raise ValueError(f"encode_png: blocks must be one of {sorted(_BLOCKS)} (got {blocks!r})")
+    if filter != 'auto' and filter not in (0, 1, 2, 3, 4):
+        raise ValueError(f"encode_png: filter must be 'auto' or 0..4 (got {filter!r})")
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _check_grid_size(H, W)
+    bound, ws_bytes = png_encode_bound(H, W)
+    nseg = len(png_encode_segments(H, W))
+    cap = bound if _BLOCKS[blocks] < 2 else 64 + nseg * (12 + PNG_ENCODE_SLOT)
+    dev = grid.device
+    src = grid.contiguous()
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    small = torch.zeros(1 + 4 * nseg, dtype=torch.int64, device=dev)          # [total length | segment table]
+    a = _lib.PngEncodeArgs(struct_bytes=ctypes.sizeof(_lib.PngEncodeArgs), H=H, W=W, blocks=_BLOCKS[blocks], filter=-1 if filter == 'auto' else int(filter), reserved=0,
+                           src=src.data_ptr(), out=out.data_ptr(), out_capacity=cap, total_bytes=small.data_ptr(),
+                           workspace=ws.data_ptr(), workspace_bytes=ws_bytes, seg_table=small.data_ptr() + 8, seg_table_rows=nseg)
+    core.check(core.lib().ldetr_png_encode_u8(ctypes.byref(a), core.stream()), 'png_encode_u8')
+    if return_stats:
+        small_h = small.cpu()
+        n = int(small_h[0])
+    else:
+        n = int(small[0].item())
+    if n <= 0 or n > cap:
+        raise RuntimeError(f'encode_png: the file needs {-n} bytes, the buffer holds {cap}')
+    data = out[:n].cpu()
+    if return_stats:
+        return data, dict(segments=small_h[1:].reshape(nseg, 4).numpy().copy(), bytes_to_host=n + small_h.numel() * 8, bound=bound)
+    return data
+
+
+def save_png(grid, path, encoder=None):
+    """Write a uint8 [H, W, 3] grid as a PNG.  encoder 'pillow' (the default): one device-to-host copy of the pixels, then PIL encodes; 'device':
+    encode_png on the GPU, only the file's bytes cross to the host.  None reads the environment variable LDETR_SNAPSHOT_PNG (unset: 'pillow')."""
     if grid.dtype != torch.uint8 or grid.ndim != 3 or grid.shape[2] != 3:
         raise ValueError('save_png: expected a uint8 [H, W, 3] grid')
+    if encoder is None:
+        import os
+        encoder = os.environ.get(PNG_ENV, '') or 'pillow'
+        if encoder not in ('pillow', 'device'):
+            raise ValueError(f"{PNG_ENV} must be 'pillow' or 'device' (got {encoder!r})")
+    elif encoder not in ('pillow', 'device'):
+        raise ValueError(f"save_png: encoder must be 'pillow', 'device' or None for {PNG_ENV} (got {encoder!r})")
+    if encoder == 'device':
+        data = encode_png(grid).numpy()
+        with open(path, 'wb') as f:
+            f.write(memoryview(data))
+        return
+    import PIL.Image
     PIL.Image.fromarray(grid.detach().cpu().numpy(), 'RGB').save(path)
 
 
