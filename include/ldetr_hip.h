@@ -407,7 +407,8 @@ int ldetr_embedding_bwd_f32(const float* dy, const int64_t* ids, float* dweight,
 /* Page-background preprocessing of a dataset item (training/dataset_layoutganpp.py:330-338): Pillow's 8-bit Lanczos ("ANTIALIAS")
  * resize of a decoded uint8 RGB page, then (x / 255 - mean) / std in fp32, CHW.  Bit-identical to Pillow + numpy.
  * ldetr_resample_coeffs (HOST memory, no GPU work): window bounds [out][2] = (first input index, tap count) and 22-bit fixed-point
- * weights, stored tap-major [ksize][out]; call with bounds = weights = NULL to query ksize.
+ * weights, stored tap-major [ksize][out]; call with bounds = weights = NULL to query ksize.  It is ldetr_resample_coeffs_filter
+ * (below) with the Lanczos window.
  * ldetr_resize_normalize_u8: src [images][H][W][3] uint8 -> tmp [images][H][out_w][3] uint8 (scratch, horizontal pass) ->
  * out_u8 [images][out_h][out_w][3] (optional) and out_chw [images][3][out_h][out_w] fp32 (optional).  hbounds/hweights are
  * ldetr_resample_coeffs(W, out_w) and vbounds/vweights ldetr_resample_coeffs(H, out_h), copied to device memory. */
@@ -459,8 +460,8 @@ int ldetr_layout_finish_f32(const float* bbox_in, const int* num, const float* f
 
 /* Snapshot grids of layouts (util.py:85-141: convert_layout_to_image, expand2square, save_image's ToTensor / make_grid / save_image), one launch per
  * grid, bit-identical to the reference's PNG pixels (csrc/layout_raster.hip; the rule is DESIGN.md section 13).
- * ldetr_resample_coeffs_filter (HOST memory, no GPU work): ldetr_resample_coeffs with the window chosen, LDETR_FILTER_BILINEAR (Pillow's triangle
- * window, util.py:111) or LDETR_FILTER_LANCZOS (what ldetr_resample_coeffs computes).
+ * ldetr_resample_coeffs_filter (HOST memory, no GPU work): the table builder of Pillow's 8-bit resampling (csrc/pil_resample.hpp) for the window
+ * LDETR_FILTER_BILINEAR (Pillow's triangle window, util.py:111) or LDETR_FILTER_LANCZOS; ldetr_resample_coeffs is this entry with LDETR_FILTER_LANCZOS.
  * ldetr_layout_raster_cell_size (HOST): the size a W x H page is resized to inside an S x S cell (util.py:105-110, double arithmetic).
  * ldetr_layout_raster_u8: cell b draws the valid boxes of bbox[b] over a white page (page_index[b] == -1 or n_pages == 0) or over page
  * page_index[b] of the page table, resizes it and writes it letterboxed at its place in the grid `out` [Hg][Wg][3]: B == 1 gives the S x S cell

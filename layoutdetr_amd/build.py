@@ -21,7 +21,7 @@ ARCH = 'gfx950'
 
 SOURCES = ['ldetr_core.cpp', 'bias_act.hip', 'upfirdn2d.hip', 'gemm_conv.hip', 'attention.hip', 'layernorm.hip',
            'misc_ops.hip', 'optim.hip', 'lsap.hip', 'xent.hip', 'resample.hip', 'layout_loss.hip', 'demod.hip', 'wgrad_smallc.hip', 'stem_conv.hip', 'box_ops.hip', 'ffn_fused.hip', 'conv_c32.hip', 'mha_small.hip', 'p3_engine.hip', 'bmm_strided.hip', 'layoutnet.hip', 'layoutnet_train.hip', 'layout_finish.hip', 'layout_raster.hip', 'page_filter.hip', 'patch_resize.hip', 'png_decode.hip', 'png_encode.hip']
-HEADERS = ['ldetr_common.hpp', 'layoutnet_layers.hpp', os.path.join('..', '..', 'include', 'ldetr_hip.h')]
+HEADERS = ['ldetr_common.hpp', 'layoutnet_layers.hpp', 'pil_resample.hpp', os.path.join('..', '..', 'include', 'ldetr_hip.h')]
 
 # the per-block tracer of the tiled kernel (tools/trace_tiles.py) is a development build: LDETR_TILE_TRACE=1 python -m layoutdetr_amd.build --force
 # (the production kernel carries explicit sched_barrier(0) fences where the tracer's stamps used to sit)

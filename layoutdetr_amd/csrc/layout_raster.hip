@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "ldetr_common.hpp"
-#include "../../include/ldetr_hip.h"
+#include "pil_resample.hpp"
 
 #pragma clang fp contract(off)
 
@@ -41,7 +41,6 @@ constexpr int LR_IMAGE_CELL_INTS = 128;   // the image kinds' descriptor: the sa
 constexpr int LR_HBUF_BYTES = 44 * 1024;  // horizontal-pass rows of a band
 constexpr int LR_SRC_BYTES = 16 * 1024;   // source rows in flight
 constexpr int LR_MAX_BAND = 32;
-constexpr int LR_PRECISION_BITS = 32 - 8 - 2;
 
 struct LayoutRasterParams {
     const float* bbox; const unsigned char* pages; const int* coeffs; const int* cells; unsigned char* out;
@@ -52,10 +51,6 @@ __device__ __forceinline__ int lr_trunc(float f) {
     if (f >= 2147483648.f) return INT_MAX;
     if (f <= -2147483648.f) return INT_MIN;
     return f == f ? (int)f : 0;                                      // (a NaN corner: the box is skipped, the value is never used)
-}
-__device__ __forceinline__ int lr_clip8(int acc) {
-    const int v = acc >> LR_PRECISION_BITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 __device__ __forceinline__ unsigned lr_blend(unsigned c, unsigned d) {
     const unsigned t = c * 100u + d * 155u + 128u;
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
     const int cy = slot / p.xmaps, cx = slot % p.xmaps;
     const int y0 = band * R, y1 = min(y0 + R, S);
     const int W = cell[0], H = cell[1], Wn = cell[2], Hn = cell[3], ox = cell[4], oy = cell[5];
-    const long page_off = (long)cell[7] * 4294967296L + (long)(unsigned)cell[6];  // < 0: white page
+    const long page_off = get_i64(cell + 6);                          // < 0: white page
     const int hoff = cell[8], voff = cell[10];                        // < 0: the pass is skipped
     const int ys = live ? max(y0 - oy, 0) : 0, ye = live ? min(y1 - oy, Hn) : 0;   // rows of the resized page in this band
     int rlo = 0;
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
                 int rank = 0;
                 for (int j = 0; j < LR_MAX_N; j++) rank += (bok[j] && (barea[j] > a || (barea[j] == a && j < tid))) ? 1 : 0;
                 bx[rank][0] = X1; bx[rank][1] = Y1; bx[rank][2] = X2; bx[rank][3] = Y2;
-                if constexpr (IMAGE) boff[rank] = (long)cell[32 + 6 * tid + 5] * 4294967296L + (long)(unsigned)cell[32 + 6 * tid + 4];
+                if constexpr (IMAGE) boff[rank] = get_i64(cell + 32 + 6 * tid + 4);
                 else bcol[rank] = (unsigned)cell[16 + tid];
             }
         }
@@ -170,14 +165,10 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
                 for (int i = tid; i < nr * Wn; i += LR_THREADS) {
                     const int row = i / Wn, xx = i % Wn;
                     const int xmin = hb[2 * xx], cnt = hb[2 * xx + 1];
-                    const unsigned char* px = sbuf + (row * W + xmin) * 3;
-                    int a0 = 1 << (LR_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-                    for (int t = 0; t < cnt; t++) {
-                        const int k = hk[t * Wn + xx];
-                        a0 += px[3 * t] * k; a1 += px[3 * t + 1] * k; a2 += px[3 * t + 2] * k;
-                    }
+                    int a0 = PIL_HALF, a1 = a0, a2 = a0;
+                    pil_taps3<3>(sbuf + (row * W + xmin) * 3, 0, hk, Wn, xx, cnt, a0, a1, a2);
                     unsigned char* o = hbuf + ((r0 - rlo + row) * Wn + xx) * 3;
-                    o[0] = (unsigned char)lr_clip8(a0); o[1] = (unsigned char)lr_clip8(a1); o[2] = (unsigned char)lr_clip8(a2);
+                    o[0] = (unsigned char)pil_clip8(a0); o[1] = (unsigned char)pil_clip8(a1); o[2] = (unsigned char)pil_clip8(a2);
                 }
             }
         }
@@ -201,14 +192,9 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
                 v0 = px[0]; v1 = px[1]; v2 = px[2];
             } else {
                 const int ymin = vb[2 * yy], cnt = vb[2 * yy + 1];
-                const unsigned char* px = hbuf + ((ymin - rlo) * Wn + xx) * 3;
-                int a0 = 1 << (LR_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-                for (int t = 0; t < cnt; t++) {
-                    const int k = vk[t * Hn + yy];
-                    a0 += px[0] * k; a1 += px[1] * k; a2 += px[2] * k;
-                    px += Wn * 3;
-                }
-                v0 = lr_clip8(a0); v1 = lr_clip8(a1); v2 = lr_clip8(a2);
+                int a0 = PIL_HALF, a1 = a0, a2 = a0;
+                pil_taps3<0>(hbuf + ((ymin - rlo) * Wn + xx) * 3, Wn * 3, vk, Hn, yy, cnt, a0, a1, a2);
+                v0 = pil_clip8(a0); v1 = pil_clip8(a1); v2 = pil_clip8(a2);
             }
         }
         unsigned char* o = p.out + ((long)gy * p.Wg + gx) * 3;
@@ -216,72 +202,15 @@ __global__ __launch_bounds__(LR_THREADS) void layout_raster_kernel(LayoutRasterP
     }
 }
 
-// Pillow's resampling windows (src/libImaging/Resample.c precompute_coeffs) as 22-bit fixed point, tap-major
-static double rs2_sinc(double x) {
-    if (x == 0.0) return 1.0;
-    x = x * M_PI;
-    return sin(x) / x;
-}
-static double rs2_lanczos3(double x) { return (-3.0 <= x && x < 3.0) ? rs2_sinc(x) * rs2_sinc(x / 3.0) : 0.0; }
-static double rs2_bilinear(double x) {
-    if (x < 0.0) x = -x;
-    return x < 1.0 ? 1.0 - x : 0.0;
-}
-
 }  // namespace ldetr
 
 using namespace ldetr;
-
-extern "C" int ldetr_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t* bounds, int32_t* kk, int64_t kk_capacity, int* ksize_out) {
-    LDETR_CHECK(filter == LDETR_FILTER_BILINEAR || filter == LDETR_FILTER_LANCZOS, "resample_coeffs_filter: unknown filter %d (0 bilinear, 1 lanczos)", filter);
-    LDETR_CHECK(in_size > 0 && out_size > 0 && ksize_out, "resample_coeffs_filter: bad arguments");
-    double (*window)(double) = filter == LDETR_FILTER_BILINEAR ? rs2_bilinear : rs2_lanczos3;
-    const double scale = (double)in_size / out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = (filter == LDETR_FILTER_BILINEAR ? 1.0 : 3.0) * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
-    *ksize_out = ksize;
-    if (!bounds && !kk) return LDETR_OK;                        // size query
-    LDETR_CHECK(bounds && kk && kk_capacity >= (int64_t)ksize * out_size, "resample_coeffs_filter: weight buffer too small (need ksize * out_size ints)");
-    const double ss = 1.0 / filterscale;
-    std::vector<double> w(ksize);
-    for (int xx = 0; xx < out_size; xx++) {
-        const double center = 0.0 + (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5); if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5); if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        double ww = 0.0;
-        for (int x = 0; x < xmax; x++) { w[x] = window((x + xmin - center + 0.5) * ss); ww += w[x]; }
-        for (int x = 0; x < ksize; x++) {
-            int q = 0;
-            if (x < xmax) {
-                const double v = ww != 0.0 ? w[x] / ww : w[x];
-                q = v < 0 ? (int)(-0.5 + v * (1 << LR_PRECISION_BITS)) : (int)(0.5 + v * (1 << LR_PRECISION_BITS));
-            }
-            kk[(int64_t)x * out_size + xx] = q;                 // tap-major
-        }
-        bounds[2 * xx] = xmin; bounds[2 * xx + 1] = xmax;
-    }
-    return LDETR_OK;
-}
 
 extern "C" int ldetr_layout_raster_cell_size(int W, int H, int S, int* wn_out, int* hn_out) {
     LDETR_CHECK(wn_out && hn_out, "layout_raster_cell_size: null output");
     LDETR_CHECK(W >= 1 && H >= 1 && S >= 1, "layout_raster_cell_size: page and canvas sizes must be positive (got %d x %d -> %d)", W, H, S);
     if (W > H) { *wn_out = S; *hn_out = (int)((double)H / (double)W * (double)S) / 2 * 2; }
     else { *hn_out = S; *wn_out = (int)((double)W / (double)H * (double)S) / 2 * 2; }
-    return LDETR_OK;
-}
-
-// make_grid's layout (rule 7) for B cells of S x S
-static int lr_grid_dims(const char* who, int B, int nrow_arg, int S, int* xmaps, int* ymaps, int* pad, long* Hg, long* Wg) {
-    *xmaps = 1; *ymaps = 1; *pad = 0;
-    if (B > 1) {
-        int nrow = nrow_arg > 0 ? nrow_arg : (int)ceil(sqrt((double)B));
-        *xmaps = nrow < B ? nrow : B; *ymaps = (B + *xmaps - 1) / *xmaps; *pad = 2;
-    }
-    *Hg = (long)*ymaps * (S + *pad) + *pad; *Wg = (long)*xmaps * (S + *pad) + *pad;
-    LDETR_CHECK(*Hg * *Wg * 3 < (1L << 31) && (long)*xmaps * *ymaps <= 65535, "%s: grid too large (%ld x %ld)", who, *Hg, *Wg);
     return LDETR_OK;
 }
 
@@ -314,31 +243,58 @@ static int lr_cell_geometry(const char* who, int b, int W, int H, int S, const i
     return LDETR_OK;
 }
 
-extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* stream) {
-    LDETR_CHECK(a, "layout_raster: null argument block");
-    LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_layout_raster_args), "layout_raster: argument block of %d bytes, this library expects %d", a->struct_bytes,
-                (int)sizeof(ldetr_layout_raster_args));
+// Both raster entries: the shared checks, make_grid's layout (rule 7), one descriptor per cell, its upload and the launch.  `what` names a slot in
+// the messages; `check()` holds an entry's own argument checks; `fill(b, W, H, c, off, mask)` writes a cell's kind-specific words into c and
+// gives the byte offset of its page (-1: white) and the mask of the slots it draws.
+template <bool IMAGE, typename Args, typename Check, typename Fill>
+static int lr_raster(const char* who, const char* what, const Args* a, const uint8_t* pages, void* stream, Check check, Fill fill) {
+    constexpr int CI = IMAGE ? LR_IMAGE_CELL_INTS : LR_CELL_INTS;
     const int B = a->B, N = a->N, S = a->S;
-    LDETR_CHECK(B >= 0, "layout_raster: negative B (got %d)", B);
-    LDETR_CHECK(N >= 1 && N <= LR_MAX_N, "layout_raster: needs 1 <= N <= 16 boxes per layout (got %d)", N);
-    LDETR_CHECK(S >= 2 && S % 2 == 0 && S <= 4096, "layout_raster: the canvas size must be even and in [2, 4096] (got %d)", S);
+    LDETR_CHECK(B >= 0, "%s: negative B (got %d)", who, B);
+    LDETR_CHECK(N >= 1 && N <= LR_MAX_N, "%s: needs 1 <= N <= 16 %s per layout (got %d)", who, what, N);
+    LDETR_CHECK(S >= 2 && S % 2 == 0 && S <= 4096, "%s: the canvas size must be even and in [2, 4096] (got %d)", who, S);
     if (B == 0) return LDETR_OK;
-    LDETR_CHECK(a->bbox && a->valid && a->labels && a->palette && a->page_wh && a->cell_coeffs && a->coeffs && a->cells_dev && a->out,
-                "layout_raster: null pointer");
-    LDETR_CHECK(a->n_colors >= 1, "layout_raster: empty palette");
-    LDETR_CHECK(a->n_pages >= 0 && (a->n_pages == 0 || (a->pages && a->page_table && a->page_index)), "layout_raster: pages given without buffer, table or index");
-    int xmaps, ymaps, pad;
-    long Hg, Wg;
-    if (int rc = lr_grid_dims("layout_raster", B, a->nrow, S, &xmaps, &ymaps, &pad, &Hg, &Wg)) return rc;
+    LDETR_CHECK(a->bbox && a->valid && a->page_wh && a->cell_coeffs && a->coeffs && a->cells_dev && a->out, "%s: null pointer", who);
+    if (int rc = check()) return rc;
+    int xmaps = 1, ymaps = 1, pad = 0;
+    if (B > 1) {
+        const int nrow = a->nrow > 0 ? a->nrow : (int)ceil(sqrt((double)B));
+        xmaps = nrow < B ? nrow : B; ymaps = (B + xmaps - 1) / xmaps; pad = 2;
+    }
+    const long Hg = (long)ymaps * (S + pad) + pad, Wg = (long)xmaps * (S + pad) + pad;
+    LDETR_CHECK(Hg * Wg * 3 < (1L << 31) && (long)xmaps * ymaps <= 65535, "%s: grid too large (%ld x %ld)", who, Hg, Wg);
     static thread_local std::vector<int32_t> cells;                    // outlives the call: the upload below reads it
-    cells.assign((size_t)B * LR_CELL_INTS, 0);
+    cells.assign((size_t)B * CI, 0);
     int bands = 1;
     for (int b = 0; b < B; b++) {
-        int32_t* c = cells.data() + (size_t)b * LR_CELL_INTS;
+        int32_t* c = cells.data() + (size_t)b * CI;
         const int W = a->page_wh[2 * b], H = a->page_wh[2 * b + 1];
-        if (int rc = lr_cell_geometry("layout_raster", b, W, H, S, a->cell_coeffs + 4 * (long)b, a->coeffs_len, c, &bands)) return rc;
-        long off = -1;
-        const int pi = a->n_pages > 0 ? a->page_index[b] : -1;
+        if (int rc = lr_cell_geometry(who, b, W, H, S, a->cell_coeffs + 4 * (long)b, a->coeffs_len, c, &bands)) return rc;
+        int64_t off = -1;
+        unsigned mask = 0;
+        if (int rc = fill(b, W, H, c, off, mask)) return rc;
+        put_i64(c + 6, off);
+        c[12] = (int32_t)mask;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = upload_descriptors(who, a->cells_dev, cells.data(), cells.size(), st)) return rc;
+    LayoutRasterParams p; memset(&p, 0, sizeof(p));
+    p.bbox = a->bbox; p.pages = pages; p.coeffs = a->coeffs; p.cells = a->cells_dev; p.out = a->out;
+    p.B = B; p.N = N; p.S = S; p.xmaps = xmaps; p.ymaps = ymaps; p.pad = pad; p.Hg = (int)Hg; p.Wg = (int)Wg;
+    hipLaunchKernelGGL(layout_raster_kernel<IMAGE>, dim3((unsigned)bands, (unsigned)(xmaps * ymaps)), LR_THREADS, 0, st, p);
+    return check_launch(who);
+}
+
+extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* stream) {
+    LDETR_CHECK_BLOCK(a, ldetr_layout_raster_args, "layout_raster");
+    auto check = [&]() {
+        LDETR_CHECK(a->labels && a->palette, "layout_raster: null pointer");
+        LDETR_CHECK(a->n_colors >= 1, "layout_raster: empty palette");
+        LDETR_CHECK(a->n_pages >= 0 && (a->n_pages == 0 || (a->pages && a->page_table && a->page_index)), "layout_raster: pages given without buffer, table or index");
+        return LDETR_OK;
+    };
+    auto fill = [&](int b, int W, int H, int32_t* c, int64_t& off, unsigned& mask) {
+        const int N = a->N, pi = a->n_pages > 0 ? a->page_index[b] : -1;
         LDETR_CHECK(pi >= -1 && pi < a->n_pages, "layout_raster: cell %d: page index %d outside the page table (%d pages)", b, pi, a->n_pages);
         if (pi >= 0) {
             const int64_t* t = a->page_table + 3 * (long)pi;
@@ -346,7 +302,6 @@ extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* s
             LDETR_CHECK(t[0] >= 0 && t[0] + (int64_t)W * H * 3 <= a->pages_bytes, "layout_raster: cell %d: page %d reaches past the page buffer", b, pi);
             off = t[0];
         }
-        unsigned mask = 0;
         for (int i = 0; i < N; i++) {
             if (!a->valid[(long)b * N + i]) continue;
             const int lab = a->labels[(long)b * N + i];
@@ -354,44 +309,22 @@ extern "C" int ldetr_layout_raster_u8(const ldetr_layout_raster_args* a, void* s
             mask |= 1u << i;
             c[16 + i] = a->palette[3 * lab] | (a->palette[3 * lab + 1] << 8) | (a->palette[3 * lab + 2] << 16);
         }
-        c[6] = (int32_t)(off & 0xffffffffL); c[7] = (int32_t)(off >> 32);
-        c[12] = (int32_t)mask;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(a->cells_dev, cells.data(), cells.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { set_error("layout_raster: descriptor upload: %s", hipGetErrorString(e)); return LDETR_ERR_LAUNCH; }
-    LayoutRasterParams p; memset(&p, 0, sizeof(p));
-    p.bbox = a->bbox; p.pages = a->pages; p.coeffs = a->coeffs; p.cells = a->cells_dev; p.out = a->out;
-    p.B = B; p.N = N; p.S = S; p.xmaps = xmaps; p.ymaps = ymaps; p.pad = pad; p.Hg = (int)Hg; p.Wg = (int)Wg;
-    hipLaunchKernelGGL(layout_raster_kernel<false>, dim3((unsigned)bands, (unsigned)(xmaps * ymaps)), LR_THREADS, 0, st, p);
-    return check_launch("layout_raster");
+        return LDETR_OK;
+    };
+    return lr_raster<false>("layout_raster", "boxes", a, a->pages, stream, check, fill);
 }
 
 extern "C" int ldetr_image_raster_u8(const ldetr_image_raster_args* a, void* stream) {
-    LDETR_CHECK(a, "image_raster: null argument block");
-    LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_image_raster_args), "image_raster: argument block of %d bytes, this library expects %d", a->struct_bytes,
-                (int)sizeof(ldetr_image_raster_args));
-    const int B = a->B, N = a->N, S = a->S;
-    LDETR_CHECK(B >= 0, "image_raster: negative B (got %d)", B);
-    LDETR_CHECK(N >= 1 && N <= LR_MAX_N, "image_raster: needs 1 <= N <= 16 elements per layout (got %d)", N);
-    LDETR_CHECK(S >= 2 && S % 2 == 0 && S <= 4096, "image_raster: the canvas size must be even and in [2, 4096] (got %d)", S);
-    if (B == 0) return LDETR_OK;
-    LDETR_CHECK(a->bbox && a->valid && a->rects && a->patch_off && a->page_off && a->page_wh && a->cell_coeffs && a->coeffs && a->cells_dev && a->out,
-                "image_raster: null pointer");
-    LDETR_CHECK(a->pixels_bytes >= 0 && (a->pixels || a->pixels_bytes == 0), "image_raster: pixel buffer size without buffer");
-    int xmaps, ymaps, pad;
-    long Hg, Wg;
-    if (int rc = lr_grid_dims("image_raster", B, a->nrow, S, &xmaps, &ymaps, &pad, &Hg, &Wg)) return rc;
-    static thread_local std::vector<int32_t> cells;
-    cells.assign((size_t)B * LR_IMAGE_CELL_INTS, 0);
-    int bands = 1;
-    for (int b = 0; b < B; b++) {
-        int32_t* c = cells.data() + (size_t)b * LR_IMAGE_CELL_INTS;
-        const int W = a->page_wh[2 * b], H = a->page_wh[2 * b + 1];
-        if (int rc = lr_cell_geometry("image_raster", b, W, H, S, a->cell_coeffs + 4 * (long)b, a->coeffs_len, c, &bands)) return rc;
-        const int64_t off = a->page_off[b];
+    LDETR_CHECK_BLOCK(a, ldetr_image_raster_args, "image_raster");
+    auto check = [&]() {
+        LDETR_CHECK(a->rects && a->patch_off && a->page_off, "image_raster: null pointer");
+        LDETR_CHECK(a->pixels_bytes >= 0 && (a->pixels || a->pixels_bytes == 0), "image_raster: pixel buffer size without buffer");
+        return LDETR_OK;
+    };
+    auto fill = [&](int b, int W, int H, int32_t* c, int64_t& off, unsigned& mask) {
+        const int N = a->N;
+        off = a->page_off[b];
         LDETR_CHECK(off >= -1 && (off < 0 || off + (int64_t)W * H * 3 <= a->pixels_bytes), "image_raster: cell %d: resized background reaches past the pixel buffer", b);
-        unsigned mask = 0;
         for (int i = 0; i < N; i++) {
             if (!a->valid[(long)b * N + i]) continue;
             const int32_t* r = a->rects + ((long)b * N + i) * 4;           // the UNCLIPPED paste rectangle: the patch is (y2 - y1) x (x2 - x1)
@@ -402,17 +335,9 @@ extern "C" int ldetr_image_raster_u8(const ldetr_image_raster_args* a, void* str
             mask |= 1u << i;
             int32_t* e = c + 32 + 6 * i;
             e[0] = r[0]; e[1] = r[1]; e[2] = r[2]; e[3] = r[3];             // (the kernel only visits page pixels: that is the clip)
-            e[4] = (int32_t)(po & 0xffffffffL); e[5] = (int32_t)(po >> 32);
+            put_i64(e + 4, po);
         }
-        c[6] = (int32_t)(off & 0xffffffffL); c[7] = (int32_t)(off >> 32);
-        c[12] = (int32_t)mask;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(a->cells_dev, cells.data(), cells.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { set_error("image_raster: descriptor upload: %s", hipGetErrorString(e)); return LDETR_ERR_LAUNCH; }
-    LayoutRasterParams p; memset(&p, 0, sizeof(p));
-    p.bbox = a->bbox; p.pages = a->pixels; p.coeffs = a->coeffs; p.cells = a->cells_dev; p.out = a->out;
-    p.B = B; p.N = N; p.S = S; p.xmaps = xmaps; p.ymaps = ymaps; p.pad = pad; p.Hg = (int)Hg; p.Wg = (int)Wg;
-    hipLaunchKernelGGL(layout_raster_kernel<true>, dim3((unsigned)bands, (unsigned)(xmaps * ymaps)), LR_THREADS, 0, st, p);
-    return check_launch("image_raster");
+        return LDETR_OK;
+    };
+    return lr_raster<true>("image_raster", "elements", a, a->pixels, stream, check, fill);
 }

@@ -68,7 +68,28 @@ inline int check_launch(const char* what) {
         }                                         \
     } while (0)
 
+// the head of every argument-block entry: a null block, or one laid out by another version of include/ldetr_hip.h
+#define LDETR_CHECK_BLOCK(a, type, who)                                                                                               \
+    do {                                                                                                                              \
+        LDETR_CHECK(a, "%s: null argument block", who);                                                                               \
+        LDETR_CHECK((a)->struct_bytes == (int)sizeof(type), "%s: argument block of %d bytes, this library expects %d", who, (a)->struct_bytes, \
+                    (int)sizeof(type));                                                                                               \
+    } while (0)
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Per-cell / per-job descriptors of int32 words (layout_raster.hip, patch_resize.hip): a 64-bit byte offset travels as (low word, high word);
+// the host vector is uploaded on the launch's stream and must outlive the call.
+inline void put_i64(int32_t* w, int64_t v) { w[0] = (int32_t)(v & 0xffffffffL); w[1] = (int32_t)(v >> 32); }
+__device__ __forceinline__ long get_i64(const int* w) { return (long)w[1] * 4294967296L + (long)(unsigned)w[0]; }
+inline int upload_descriptors(const char* who, int32_t* dev, const int32_t* host, size_t count, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(dev, host, count * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+        set_error("%s: descriptor upload: %s", who, hipGetErrorString(e));
+        return LDETR_ERR_LAUNCH;
+    }
+    return LDETR_OK;
+}
 
 // Counter-based RNG over (seed, element index): the same pair is evaluated in forward and backward, so dropout masks are
 // regenerated rather than stored.  32-bit mixing (murmur3 finaliser over the folded index, keyed by both seed halves): two

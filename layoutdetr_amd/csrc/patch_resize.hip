@@ -79,8 +79,8 @@ __global__ __launch_bounds__(PR_THREADS) void patch_resize_kernel(PatchResizePar
     const int rows = Cs * 3, rowg = Cg * 3, rowo = nTx * 3;
     if (gy0 < 0 || gx0 < 0 || gy1 >= h || gx1 >= w || (long)Rs * rows > PR_A_FLOATS || (long)Rg * rows > PR_B_FLOATS || (long)nTy * rowg > PR_B_FLOATS)
         return;                                                      // (never: the host sized the tile for it and checked the indices)
-    const unsigned char* src = (j[14] ? p.src1 : p.src0) + ((long)j[1] * 4294967296L + (long)(unsigned)j[0]);
-    unsigned char* dst = p.dst + ((long)j[5] * 4294967296L + (long)(unsigned)j[4]);
+    const unsigned char* src = (j[14] ? p.src1 : p.src0) + get_i64(j);
+    unsigned char* dst = p.dst + get_i64(j + 4);
     // 0. the source window, u8 / 255
     for (int i = tid; i < Rs * rows; i += PR_THREADS) {
         const int r = i / rows, c = i - r * rows;
@@ -149,9 +149,7 @@ static void pr_extents(const int32_t* i0, const int32_t* i1, int out, int T, int
 using namespace ldetr;
 
 extern "C" int ldetr_patch_resize_u8(const ldetr_patch_resize_args* a, void* stream) {
-    LDETR_CHECK(a, "patch_resize: null argument block");
-    LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_patch_resize_args), "patch_resize: argument block of %d bytes, this library expects %d", a->struct_bytes,
-                (int)sizeof(ldetr_patch_resize_args));
+    LDETR_CHECK_BLOCK(a, ldetr_patch_resize_args, "patch_resize");
     const int J = a->n_jobs;
     LDETR_CHECK(J >= 0 && J <= 65535, "patch_resize: 0 <= jobs <= 65535 (got %d)", J);
     if (J == 0) return LDETR_OK;
@@ -200,16 +198,15 @@ extern "C" int ldetr_patch_resize_u8(const ldetr_patch_resize_args* a, void* str
             else Ty = (Ty + 1) / 2;
         }
         int32_t* c = jobs.data() + (size_t)k * PR_JOB_INTS;
-        c[0] = (int32_t)(q[1] & 0xffffffffL); c[1] = (int32_t)(q[1] >> 32); c[2] = h; c[3] = w;
-        c[4] = (int32_t)(q[4] & 0xffffffffL); c[5] = (int32_t)(q[4] >> 32); c[6] = ho; c[7] = wo;
+        put_i64(c, q[1]); c[2] = h; c[3] = w;
+        put_i64(c + 4, q[4]); c[6] = ho; c[7] = wo;
         c[8] = (int32_t)q[7]; c[9] = (int32_t)q[8]; c[10] = Ty; c[11] = Tx;
         c[12] = (wo + Tx - 1) / Tx; c[13] = (ho + Ty - 1) / Ty; c[14] = (int32_t)q[0];
         tiles = std::max(tiles, (long)c[12] * c[13]);
     }
     LDETR_CHECK(a->tables_len < (1L << 31), "patch_resize: table pool too large");
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(a->jobs_dev, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { set_error("patch_resize: descriptor upload: %s", hipGetErrorString(e)); return LDETR_ERR_LAUNCH; }
+    if (int rc = upload_descriptors("patch_resize", a->jobs_dev, jobs.data(), jobs.size(), st)) return rc;
     PatchResizeParams p;
     p.src0 = a->src0; p.src1 = a->src1; p.dst = a->dst; p.tables = a->tables; p.jobs = a->jobs_dev;
     hipLaunchKernelGGL(patch_resize_kernel, dim3((unsigned)tiles, (unsigned)J), PR_THREADS, 0, st, p);

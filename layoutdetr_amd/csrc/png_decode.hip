@@ -398,9 +398,7 @@ __global__ void __launch_bounds__(PNG_THREADS) png_unfilter_kernel(PngParams p) 
 }  // namespace ldetr
 
 extern "C" int ldetr_png_decode_u8(const ldetr_png_decode_args* a, void* stream) {
-    LDETR_CHECK(a, "png_decode: null argument block");
-    LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_png_decode_args), "png_decode: argument block of %d bytes, this library expects %d", a->struct_bytes,
-                (int)sizeof(ldetr_png_decode_args));
+    LDETR_CHECK_BLOCK(a, ldetr_png_decode_args, "png_decode");
     const int n = a->n, H = a->H, W = a->W;
     LDETR_CHECK(n >= 0 && n <= 65535, "png_decode: 0 <= pages <= 65535 (got %d)", n);
     if (n == 0) return LDETR_OK;

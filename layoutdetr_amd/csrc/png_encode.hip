@@ -705,9 +705,7 @@ extern "C" int ldetr_png_encode_bound(int H, int W, int64_t* out_bytes, int64_t*
 }
 
 extern "C" int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream) {
-    LDETR_CHECK(a, "png_encode: null argument block");
-    LDETR_CHECK(a->struct_bytes == (int)sizeof(ldetr_png_encode_args), "png_encode: argument block of %d bytes, this library expects %d", a->struct_bytes,
-                (int)sizeof(ldetr_png_encode_args));
+    LDETR_CHECK_BLOCK(a, ldetr_png_encode_args, "png_encode");
     const int H = a->H, W = a->W;
     LDETR_CHECK(W >= 1 && W <= PE_MAX_DIM && H >= 1 && H <= PE_MAX_DIM, "png_encode: grid %d x %d outside [1, %d] x [1, %d]", W, H, PE_MAX_DIM, PE_MAX_DIM);
     LDETR_CHECK(a->blocks >= 0 && a->blocks <= 3, "png_encode: blocks %d (0 auto, 1 stored, 2 fixed, 3 dynamic)", a->blocks);

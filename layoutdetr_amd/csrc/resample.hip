@@ -3,8 +3,8 @@
 //     background = (background.astype(np.float32) / 255.0 - rgb_mean) / rgb_std      :335
 //     background = background.transpose(2, 0, 1)                                     :336
 // The resize is Pillow's 8-bit two-pass resampling (src/libImaging/Resample.c, Pillow==9.3.0 in the reference's environment.yaml:46)
-// with the Lanczos-3 window: per output coordinate a window of weights (double, normalised, 22-bit fixed point, round half away
-// from zero), out = clip8((2^21 + sum px * k) >> 22); horizontal pass into a uint8 intermediate, then the vertical pass.  Integer
+// with the Lanczos-3 window (the rule -- windows, 22-bit weights, tap accumulation, clip -- is pil_resample.hpp): horizontal pass
+// into a uint8 intermediate, then the vertical pass.  Integer
 // arithmetic end to end, so the device result is bit-identical to Pillow's; the fp32 normalisation uses correctly rounded
 // division / subtraction in the reference's order, so the float tensor is bit-identical too.
 //
@@ -13,14 +13,11 @@
 // of the horizontal pass (ablation: without the LDS reads 85 of 144 us remain, the bare multiply-add loop is 57 us).  Horizontal pass: one block per (row, 256 output columns), the row segment staged in LDS with 4-byte loads;
 // vertical pass: plane-major threads so the float stores are fully coalesced.  Weights are stored tap-major ([ksize][out]) so
 // neighbouring lanes read neighbouring weights.
-#include <math.h>
-
 #include "ldetr_common.hpp"
-#include "../../include/ldetr_hip.h"
+#include "pil_resample.hpp"
 
 namespace ldetr {
 
-constexpr int RS_PRECISION_BITS = 32 - 8 - 2;
 constexpr int RS_LDS_BYTES = 48 * 1024;
 
 struct ResampleParams {
@@ -32,11 +29,6 @@ struct ResampleParams {
     int lds_bytes;
     float mean[3], stdv[3];
 };
-
-__device__ __forceinline__ int clip8(int acc) {
-    const int v = acc >> RS_PRECISION_BITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 // grid (ceil(OW / 256), H, images)
 __global__ __launch_bounds__(256) void resample_h_kernel(ResampleParams p) {
@@ -67,22 +59,11 @@ __global__ __launch_bounds__(256) void resample_h_kernel(ResampleParams p) {
     const int xx = x0 + threadIdx.x;
     if (xx >= p.OW) return;
     const int xmin = p.hb[2 * xx], cnt = p.hb[2 * xx + 1];
-    int a0 = 1 << (RS_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    if (staged) {
-        const unsigned char* px = rs_row + lead + (xmin - first) * 3;
-        for (int t = 0; t < cnt; t++) {
-            const int k = p.hk[(long)t * p.OW + xx];
-            a0 += px[3 * t] * k; a1 += px[3 * t + 1] * k; a2 += px[3 * t + 2] * k;
-        }
-    } else {
-        const unsigned char* px = p.src + ((img * p.H + y) * (long)p.W + xmin) * 3;
-        for (int t = 0; t < cnt; t++) {
-            const int k = p.hk[(long)t * p.OW + xx];
-            a0 += px[3 * t] * k; a1 += px[3 * t + 1] * k; a2 += px[3 * t + 2] * k;
-        }
-    }
     unsigned char* o = p.tmp + ((img * p.H + y) * (long)p.OW + xx) * 3;
-    o[0] = (unsigned char)clip8(a0); o[1] = (unsigned char)clip8(a1); o[2] = (unsigned char)clip8(a2);
+    int a0 = PIL_HALF, a1 = a0, a2 = a0;
+    if (staged) pil_taps3<3>(rs_row + lead + (xmin - first) * 3, 0, p.hk, (long)p.OW, xx, cnt, a0, a1, a2);
+    else pil_taps3<3>(p.src + ((img * p.H + y) * (long)p.W + xmin) * 3, 0, p.hk, (long)p.OW, xx, cnt, a0, a1, a2);
+    o[0] = (unsigned char)pil_clip8(a0); o[1] = (unsigned char)pil_clip8(a1); o[2] = (unsigned char)pil_clip8(a2);
 }
 
 // grid (ceil(OW / 256), OH, images * 3): one colour plane per block so the float stores are contiguous
@@ -94,7 +75,7 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(ResampleParams p) 
     const int ymin = p.vb[2 * yy], cnt = p.vb[2 * yy + 1];
     const unsigned char* col = p.tmp + ((img * p.H + ymin) * (long)p.OW + x) * 3 + c;
     const long pitch = (long)p.OW * 3;
-    int acc = 1 << (RS_PRECISION_BITS - 1);
+    int acc = PIL_HALF;
     if (p.vks <= 32) {                          // every tap's byte load in flight at once (8-bit x 23-bit: the 24-bit multiply is full rate)
         int v[32];
 #pragma unroll
@@ -105,7 +86,7 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(ResampleParams p) 
     } else {
         for (int t = 0; t < cnt; t++) acc += __mul24((int)col[t * pitch], p.vk[(long)t * p.OH + yy]);
     }
-    const int u8 = clip8(acc);
+    const int u8 = pil_clip8(acc);
     if (p.out_u8) p.out_u8[((img * p.OH + yy) * (long)p.OW + x) * 3 + c] = (unsigned char)u8;
     if (p.out_chw) {
         const float v = __fdiv_rn(__fsub_rn(__fdiv_rn((float)u8, 255.0f), p.mean[c]), p.stdv[c]);
@@ -113,47 +94,27 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(ResampleParams p) 
     }
 }
 
-static double rs_sinc(double x) {
-    if (x == 0.0) return 1.0;
-    x = x * M_PI;
-    return sin(x) / x;
-}
-static double rs_lanczos3(double x) { return (-3.0 <= x && x < 3.0) ? rs_sinc(x) * rs_sinc(x / 3.0) : 0.0; }
-
 }  // namespace ldetr
 
 using namespace ldetr;
 
-extern "C" int ldetr_resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk, int64_t kk_capacity, int* ksize_out) {
-    LDETR_CHECK(in_size > 0 && out_size > 0 && ksize_out, "resample_coeffs: bad arguments");
-    const double scale = (double)in_size / out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 3.0 * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
-    *ksize_out = ksize;
+// the two exported table builders: argument checks around pil_resample.hpp's pil_coeffs (HOST memory, no GPU work)
+static int rs_coeffs(const char* who, int filter, int in_size, int out_size, int32_t* bounds, int32_t* kk, int64_t kk_capacity, int* ksize_out) {
+    LDETR_CHECK(in_size > 0 && out_size > 0 && ksize_out, "%s: bad arguments", who);
+    const int ksize = *ksize_out = pil_ksize(filter, in_size, out_size);
     if (!bounds && !kk) return LDETR_OK;                        // size query
-    LDETR_CHECK(bounds && kk && kk_capacity >= (int64_t)ksize * out_size, "resample_coeffs: weight buffer too small (need ksize * out_size ints)");
-    const double ss = 1.0 / filterscale;
-    double* w = new double[ksize];
-    for (int xx = 0; xx < out_size; xx++) {
-        const double center = 0.0 + (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5); if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5); if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        double ww = 0.0;
-        for (int x = 0; x < xmax; x++) { w[x] = rs_lanczos3((x + xmin - center + 0.5) * ss); ww += w[x]; }
-        for (int x = 0; x < ksize; x++) {
-            int q = 0;
-            if (x < xmax) {
-                const double v = ww != 0.0 ? w[x] / ww : w[x];
-                q = v < 0 ? (int)(-0.5 + v * (1 << RS_PRECISION_BITS)) : (int)(0.5 + v * (1 << RS_PRECISION_BITS));
-            }
-            kk[(int64_t)x * out_size + xx] = q;                 // tap-major
-        }
-        bounds[2 * xx] = xmin; bounds[2 * xx + 1] = xmax;
-    }
-    delete[] w;
+    LDETR_CHECK(bounds && kk && kk_capacity >= (int64_t)ksize * out_size, "%s: weight buffer too small (need ksize * out_size ints)", who);
+    pil_coeffs(filter, in_size, out_size, bounds, kk);
     return LDETR_OK;
+}
+
+extern "C" int ldetr_resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk, int64_t kk_capacity, int* ksize_out) {
+    return rs_coeffs("resample_coeffs", LDETR_FILTER_LANCZOS, in_size, out_size, bounds, kk, kk_capacity, ksize_out);
+}
+
+extern "C" int ldetr_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t* bounds, int32_t* kk, int64_t kk_capacity, int* ksize_out) {
+    LDETR_CHECK(filter == LDETR_FILTER_BILINEAR || filter == LDETR_FILTER_LANCZOS, "resample_coeffs_filter: unknown filter %d (0 bilinear, 1 lanczos)", filter);
+    return rs_coeffs("resample_coeffs_filter", filter, in_size, out_size, bounds, kk, kk_capacity, ksize_out);
 }
 
 extern "C" int ldetr_resize_normalize_u8(const uint8_t* src, int64_t images, int H, int W, int out_h, int out_w, const int32_t* hbounds,
@@ -174,7 +135,7 @@ extern "C" int ldetr_resize_normalize_u8(const uint8_t* src, int64_t images, int
     p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
     hipStream_t st = (hipStream_t)stream;
     // LDS for the widest row segment a block of 256 output columns can need (falls back to direct reads beyond 48 KiB)
-    const double scale = (double)W / out_w, support = 3.0 * (scale < 1.0 ? 1.0 : scale);
+    const double scale = (double)W / out_w, support = pil_support(LDETR_FILTER_LANCZOS) * (scale < 1.0 ? 1.0 : scale);
     long lds = ((long)(256.0 * scale + 2.0 * support) + 4) * 3 + 16;
     p.lds_bytes = (int)(lds > RS_LDS_BYTES ? RS_LDS_BYTES : (lds + 15) / 16 * 16);
     hipLaunchKernelGGL(resample_h_kernel, dim3(cdiv(out_w, 256), H, (unsigned)images), 256, p.lds_bytes, st, p);

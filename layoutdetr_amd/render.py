@@ -14,11 +14,10 @@ import torch
 
 from . import _lib
 from .hip import core
+from .pil_coeffs import FILTER_BILINEAR, coeff_table
 
-FILTER_BILINEAR, FILTER_LANCZOS = 0, 1
 MAX_BOXES = 16
 
-_table_cache = {}   # (in, out) -> int32 [2 * out + ksize * out] host table
 _pool_cache = {}    # (tuple of (in, out), device) -> (device pool, {pair: (offset, ksize)})
 
 
@@ -40,18 +39,6 @@ def grid_shape(B, canvas, nrow=None):
     return ymaps * (canvas + 2) + 2, xmaps * (canvas + 2) + 2, xmaps, ymaps
 
 
-def bilinear_coeffs(in_size, out_size, filter=FILTER_BILINEAR):
-    """(bounds [out, 2], weights [ksize, out], ksize) of Pillow's window for in_size -> out_size, host int32 (ldetr_resample_coeffs_filter)."""
-    lib = _lib.load()
-    ks = ctypes.c_int(0)
-    core.check(lib.ldetr_resample_coeffs_filter(filter, in_size, out_size, None, None, 0, ctypes.byref(ks)), 'resample_coeffs_filter')
-    bounds = np.zeros((out_size, 2), np.int32)
-    weights = np.zeros((ks.value, out_size), np.int32)
-    core.check(lib.ldetr_resample_coeffs_filter(filter, in_size, out_size, bounds.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p),
-                                                weights.size, ctypes.byref(ks)), 'resample_coeffs_filter')
-    return bounds, weights, ks.value
-
-
 def _coeff_pool(pairs, device):
     """One device pool holding the table of every distinct (in, out) pair of a grid; cached per set of pairs."""
     key = (tuple(pairs), str(device))
@@ -60,13 +47,10 @@ def _coeff_pool(pairs, device):
         return hit
     parts, where, at = [], {}, 0
     for pair in pairs:
-        t = _table_cache.get(pair)
-        if t is None:
-            b, w, ks = bilinear_coeffs(*pair)
-            t = _table_cache[pair] = (np.concatenate([b.reshape(-1), w.reshape(-1)]), ks)
-        where[pair] = (at, t[1])
-        parts.append(t[0])
-        at += t[0].size
+        b, w, ks = coeff_table(pair[0], pair[1], FILTER_BILINEAR)
+        where[pair] = (at, ks)
+        parts += [b.reshape(-1), w.reshape(-1)]
+        at += b.size + w.size
     pool = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(1, np.int32)).to(device)
     if len(_pool_cache) > 64:
         _pool_cache.clear()
@@ -99,6 +83,49 @@ def _host(x, dtype):
     return np.ascontiguousarray(np.asarray(x).astype(dtype))
 
 
+def _grid_args(who, what, bbox, canvas, nrow, why_even=''):
+    """(B, N, S) of a grid call after the checks layout_grid and image_grid share."""
+    B, N = int(bbox.shape[0]), int(bbox.shape[1])
+    S = int(canvas)
+    if N < 1 or N > MAX_BOXES:
+        raise ValueError(f'{who}: 1 <= N <= {MAX_BOXES} {what} per layout (got {N})')
+    if S < 2 or S % 2 != 0:
+        raise ValueError(f'{who}: the canvas size must be even (got {canvas}){why_even}')
+    if nrow is not None and int(nrow) < 1:
+        raise ValueError(f'{who}: nrow must be positive')
+    return B, N, S
+
+
+def _page_wh(page_wh, B):
+    """page_wh, (W, H) for every cell or [B, 2], as a host int32 [B, 2] array."""
+    wh = _host(page_wh, np.int32)
+    return np.ascontiguousarray(np.broadcast_to(wh.reshape(1, 2), (B, 2))) if wh.size == 2 else wh.reshape(B, 2)
+
+
+def _grid_buffers(who, wh, S, nrow, dev, cell_ints):
+    """What a raster entry needs beside its kind's own arrays: the device pool of the cells' coefficient tables, its rows per cell (`cc`: offset
+    and ksize of the W -> Wn and of the H -> Hn table, offset -1 for a pass whose sizes agree), the descriptor scratch and the grid [Hg, Wg, 3].
+    (image_grid has rejected a page size below 1 before it gets here: it needs the sizes earlier, for the paste rectangles.)"""
+    pairs, cell_pairs = [], []
+    for W, H in wh.tolist():
+        if W < 1 or H < 1:
+            raise ValueError(f'{who}: bad page size {W} x {H}')
+        Wn, Hn = cell_size(W, H, S)
+        if Wn < 1 or Hn < 1:
+            raise ValueError(f'{who}: a {W} x {H} page leaves no pixel at canvas size {S}')
+        hp, vp = ((W, Wn) if W != Wn else None), ((H, Hn) if H != Hn else None)
+        cell_pairs.append((hp, vp))
+        for pr in (hp, vp):
+            if pr is not None and pr not in pairs:
+                pairs.append(pr)
+    pool, where = _coeff_pool(sorted(pairs), dev)
+    cc = np.asarray([[where[hp][0] if hp else -1, where[hp][1] if hp else 0, where[vp][0] if vp else -1, where[vp][1] if vp else 0]
+                     for hp, vp in cell_pairs], np.int64)
+    Hg, Wg, _, _ = grid_shape(len(cell_pairs), S, nrow)
+    cells = torch.empty(len(cell_pairs) * cell_ints, dtype=torch.int32, device=dev)
+    return pool, cc, cells, torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=dev)
+
+
 def layout_grid(bbox, valid, labels, colors, page_wh, pages=None, page_index=None, canvas=128, nrow=None):
     """uint8 [Hg, Wg, 3] device tensor: the pixels of the PNG the reference's save_image(bbox, labels, valid, colors, path, W_page, H_page,
     size_canvas=canvas, nrow=nrow) writes, in one launch.
@@ -110,39 +137,17 @@ def layout_grid(bbox, valid, labels, colors, page_wh, pages=None, page_index=Non
     core.require_gpu(bbox)
     if bbox.ndim != 3 or bbox.shape[-1] != 4:
         raise ValueError('layout_grid: bbox must be [B, N, 4]')
-    B, N = int(bbox.shape[0]), int(bbox.shape[1])
-    S = int(canvas)
-    if N < 1 or N > MAX_BOXES:
-        raise ValueError(f'layout_grid: 1 <= N <= {MAX_BOXES} boxes per layout (got {N})')
-    if S < 2 or S % 2 != 0:
-        raise ValueError(f'layout_grid: the canvas size must be even (got {canvas}); the reference fails in torch.stack otherwise')
-    if nrow is not None and int(nrow) < 1:
-        raise ValueError('layout_grid: nrow must be positive')
+    B, N, S = _grid_args('layout_grid', 'boxes', bbox, canvas, nrow, '; the reference fails in torch.stack otherwise')
     dev = bbox.device
     if B == 0:
         return torch.zeros((0, 0, 3), dtype=torch.uint8, device=dev)
     valid_h = _host(valid, np.uint8).reshape(B, N)
     labels_h = _host(labels, np.int32).reshape(B, N)
     pal = _host(colors, np.uint8).reshape(-1, 3)
-    wh = _host(page_wh, np.int32)
-    wh = np.ascontiguousarray(np.broadcast_to(wh.reshape(1, 2), (B, 2))) if wh.size == 2 else wh.reshape(B, 2)
+    wh = _page_wh(page_wh, B)
     if labels_h[valid_h != 0].size and (labels_h[valid_h != 0].min() < 0 or labels_h[valid_h != 0].max() >= pal.shape[0]):
         raise ValueError(f'layout_grid: label outside the palette of {pal.shape[0]} colours')
-    pairs, cell_pairs = [], []
-    for W, H in wh.tolist():
-        if W < 1 or H < 1:
-            raise ValueError(f'layout_grid: bad page size {W} x {H}')
-        Wn, Hn = cell_size(W, H, S)
-        if Wn < 1 or Hn < 1:
-            raise ValueError(f'layout_grid: a {W} x {H} page leaves no pixel at canvas size {S}')
-        hp, vp = ((W, Wn) if W != Wn else None), ((H, Hn) if H != Hn else None)
-        cell_pairs.append((hp, vp))
-        for pr in (hp, vp):
-            if pr is not None and pr not in pairs:
-                pairs.append(pr)
-    pool, where = _coeff_pool(sorted(pairs), dev)
-    cc = np.asarray([[where[hp][0] if hp else -1, where[hp][1] if hp else 0, where[vp][0] if vp else -1, where[vp][1] if vp else 0]
-                     for hp, vp in cell_pairs], np.int64)
+    pool, cc, cells, out = _grid_buffers('layout_grid', wh, S, nrow, dev, 32)
     a = _lib.LayoutRasterArgs()
     a.struct_bytes = ctypes.sizeof(_lib.LayoutRasterArgs)
     a.B, a.N, a.S, a.nrow, a.n_colors = B, N, S, 0 if nrow is None else int(nrow), pal.shape[0]
@@ -159,10 +164,7 @@ def layout_grid(bbox, valid, labels, colors, page_wh, pages=None, page_index=Non
         keep += [pi, pages.table]
         a.n_pages, a.pages, a.pages_bytes = len(pages), pages.buffer.data_ptr(), pages.buffer.numel()
         a.page_table, a.page_index = pages.table.ctypes.data, pi.ctypes.data
-    Hg, Wg, _, _ = grid_shape(B, S, nrow)
     bb = core.f32c(bbox)
-    cells = torch.empty(B * 32, dtype=torch.int32, device=dev)
-    out = torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=dev)
     a.bbox, a.valid, a.labels, a.palette, a.page_wh = bb.data_ptr(), valid_h.ctypes.data, labels_h.ctypes.data, pal.ctypes.data, wh.ctypes.data
     a.coeffs, a.coeffs_len, a.cell_coeffs = pool.data_ptr(), pool.numel(), cc.ctypes.data
     a.cells_dev, a.out = cells.data_ptr(), out.data_ptr()
@@ -426,21 +428,13 @@ def image_grid(bbox_fake, bbox_real, valid, patches, page_wh, backgrounds=None, 
         raise ValueError('image_grid: bbox_fake and bbox_real must both be [B, N, 4]')
     if not isinstance(patches, PatchSet):
         raise ValueError('image_grid: patches must be a render.PatchSet')
-    B, N = int(bbox_fake.shape[0]), int(bbox_fake.shape[1])
-    S = int(canvas)
-    if N < 1 or N > MAX_BOXES:
-        raise ValueError(f'image_grid: 1 <= N <= {MAX_BOXES} elements per layout (got {N})')
-    if S < 2 or S % 2 != 0:
-        raise ValueError(f'image_grid: the canvas size must be even (got {canvas})')
-    if nrow is not None and int(nrow) < 1:
-        raise ValueError('image_grid: nrow must be positive')
+    B, N, S = _grid_args('image_grid', 'elements', bbox_fake, canvas, nrow)
     dev = bbox_fake.device
     if B == 0:
         return torch.zeros((0, 0, 3), dtype=torch.uint8, device=dev)
     core.require_gpu(patches.buffer)
     valid_h = _host(valid, np.uint8).reshape(B, N).copy()
-    wh = _host(page_wh, np.int32)
-    wh = np.ascontiguousarray(np.broadcast_to(wh.reshape(1, 2), (B, 2))) if wh.size == 2 else wh.reshape(B, 2)
+    wh = _page_wh(page_wh, B)
     if (wh < 1).any():
         raise ValueError('image_grid: bad page size')
     pidx = np.arange(B) if patch_index is None else _host(patch_index, np.int64).reshape(-1)
@@ -480,26 +474,11 @@ def image_grid(bbox_fake, bbox_real, valid, patches, page_wh, backgrounds=None, 
             if (cw, ch) != (int(real_wh[b, i, 0]), int(real_wh[b, i, 1])):
                 raise ValueError(f'image_grid: cell {b} slot {i}: the crop is {cw} x {ch}, bbox_real asks for {int(real_wh[b, i, 0])} x {int(real_wh[b, i, 1])}')
             patch_off[b, i] = job(0, off, ch, cw, y2 - y1, x2 - x1)
-    pairs, cell_pairs = [], []
-    for W, H in wh.tolist():
-        Wn, Hn = cell_size(W, H, S)
-        if Wn < 1 or Hn < 1:
-            raise ValueError(f'image_grid: a {W} x {H} page leaves no pixel at canvas size {S}')
-        hp, vp = ((W, Wn) if W != Wn else None), ((H, Hn) if H != Hn else None)
-        cell_pairs.append((hp, vp))
-        for pr in (hp, vp):
-            if pr is not None and pr not in pairs:
-                pairs.append(pr)
-    cpool, where = _coeff_pool(sorted(pairs), dev)
-    cc = np.asarray([[where[hp][0] if hp else -1, where[hp][1] if hp else 0, where[vp][0] if vp else -1, where[vp][1] if vp else 0]
-                     for hp, vp in cell_pairs], np.int64)
+    cpool, cc, cells, out = _grid_buffers('image_grid', wh, S, nrow, dev, 128)
     lib, st = core.lib(), core.stream()
     pixels = rj.launch(patches.buffer, None if backgrounds is None else backgrounds.buffer, dev)
-    Hg, Wg, _, _ = grid_shape(B, S, nrow)
     rects32 = np.ascontiguousarray(np.clip(rects, -2 ** 30, 2 ** 30).astype(np.int32))
     bb = core.f32c(bbox_fake)
-    cells = torch.empty(B * 128, dtype=torch.int32, device=dev)
-    out = torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=dev)
     a = _lib.ImageRasterArgs()
     a.struct_bytes = ctypes.sizeof(_lib.ImageRasterArgs)
     a.B, a.N, a.S, a.nrow = B, N, S, 0 if nrow is None else int(nrow)

@@ -41,6 +41,7 @@ import numpy as np
 import torch
 
 from ..hip import core
+from ..pil_coeffs import FILTER_LANCZOS, coeff_table
 
 RGB_MEAN = (0.485, 0.456, 0.406)   # dataset_layoutganpp.py:268
 RGB_STD = (0.229, 0.224, 0.225)    # dataset_layoutganpp.py:269
@@ -49,20 +50,14 @@ _coeff_cache = {}
 
 
 def resample_coeffs(in_size, out_size, device):
-    """(bounds [out, 2] int32, weights [ksize, out] int32, ksize) of Pillow's Lanczos window on `device`, computed once per
-    (in, out) on the host by the C-ABI library and cached."""
+    """(bounds [out, 2] int32, weights [ksize, out] int32, ksize) of Pillow's Lanczos window on `device`: the host table of
+    pil_coeffs.coeff_table, uploaded once per (in, out, device)."""
     key = (int(in_size), int(out_size), str(device))
     hit = _coeff_cache.get(key)
     if hit is not None:
         return hit
-    lib = core.lib()
-    ks = ctypes.c_int(0)
-    core.check(lib.ldetr_resample_coeffs(in_size, out_size, None, None, 0, ctypes.byref(ks)), 'resample_coeffs')
-    bounds = np.zeros((out_size, 2), np.int32)
-    weights = np.zeros((ks.value, out_size), np.int32)
-    core.check(lib.ldetr_resample_coeffs(in_size, out_size, bounds.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p),
-                                         weights.size, ctypes.byref(ks)), 'resample_coeffs')
-    out = (torch.from_numpy(bounds).to(device), torch.from_numpy(weights).to(device), ks.value)
+    bounds, weights, ksize = coeff_table(in_size, out_size, FILTER_LANCZOS)
+    out = (torch.tensor(bounds, device=device), torch.tensor(weights, device=device), ksize)     # copies: the host table is shared
     _coeff_cache[key] = out
     return out
 

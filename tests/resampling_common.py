@@ -529,8 +529,8 @@ def demod_reference_cached(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------------ page resize
-RS_LDS_BYTES = 48 * 1024      # csrc/resample.hip:24
-RS_UNROLLED_TAPS = 32         # :98
+RS_LDS_BYTES = 48 * 1024      # csrc/resample.hip:21
+RS_UNROLLED_TAPS = 32         # :79
 
 
 def rs_case(name, n, H, W, out_h, out_w, outputs='both', seed=0):
@@ -561,16 +561,16 @@ RESIZE_PATHS = ['h/staged', 'h/direct', 'lead0', 'lead1', 'lead2', 'lead3', 'las
 
 
 def resize_paths(c):
-    """ldetr_resize_normalize_u8 (csrc/resample.hip:177-183) and the two kernels.  Horizontal (:44-66): per block of 256 output columns the input
+    """ldetr_resize_normalize_u8 (csrc/resample.hip:138-144) and the two kernels.  Horizontal (:36-58): per block of 256 output columns the input
     span is staged in LDS when span + 8 <= lds_bytes, lead = byte offset of the span in its first word, the last word of the whole buffer is
-    assembled byte-wise when the buffer ends inside it.  Vertical (:98-107): taps unrolled up to 32."""
+    assembled byte-wise when the buffer ends inside it.  Vertical (:79-88): taps unrolled up to 32.  The tap arithmetic itself is csrc/pil_resample.hpp's."""
     n, H, W, oh, ow = c['n'], c['H'], c['W'], c['out_h'], c['out_w']
     hb, _, _ = resample_ref.precompute_coeffs(W, ow)
     _, _, vks = resample_ref.precompute_coeffs(H, oh)
     scale = W / ow
     support = 3.0 * max(scale, 1.0)
-    lds = (int(256.0 * scale + 2.0 * support) + 4) * 3 + 16                                    # :178
-    lds_bytes = RS_LDS_BYTES if lds > RS_LDS_BYTES else (lds + 15) // 16 * 16                   # :179
+    lds = (int(256.0 * scale + 2.0 * support) + 4) * 3 + 16                                    # :139
+    lds_bytes = RS_LDS_BYTES if lds > RS_LDS_BYTES else (lds + 15) // 16 * 16                   # :140
     src_bytes = n * H * W * 3
     xblocks = (ow + 255) // 256
     names = {f'xblocks{xblocks}', 'v/unrolled' if vks <= RS_UNROLLED_TAPS else 'v/loop', c['outputs']}
@@ -584,17 +584,17 @@ def resize_paths(c):
     for bx in range(xblocks):
         x0 = bx * 256
         x1 = min(x0 + 255, ow - 1)
-        first, last = int(hb[x0, 0]), int(hb[x1, 0] + hb[x1, 1])                                # :47
+        first, last = int(hb[x0, 0]), int(hb[x1, 0] + hb[x1, 1])                                # :39
         span = (last - first) * 3
-        staged = span + 8 <= lds_bytes                                                          # :50
+        staged = span + 8 <= lds_bytes                                                          # :42
         names.add('h/staged' if staged else 'h/direct')
         for row in range(n * H):
-            row_off = (row * W + first) * 3                                                     # :48
+            row_off = (row * W + first) * 3                                                     # :40
             lead = row_off & 3
             if staged:
                 names.add(f'lead{lead}')
-                words = (lead + span + 3) >> 2                                                  # :54
-                bytewise |= row_off - lead + 4 * words > src_bytes                              # :58
+                words = (lead + span + 3) >> 2                                                  # :46
+                bytewise |= row_off - lead + 4 * words > src_bytes                              # :50
     names.add('last_word/bytewise' if bytewise else 'last_word/whole')
     return names
 

@@ -361,7 +361,7 @@ def test_resize_is_bit_equal_to_the_reference(dev, name):
 
 
 def test_resize_coefficient_tables_equal_the_reference(dev):
-    """ldetr_resample_coeffs (host code of csrc/resample.hip:127-157): bounds and 22-bit weights, tap-major."""
+    """ldetr_resample_coeffs (csrc/resample.hip:102-113 around the host builder, csrc/pil_resample.hpp:59-90): bounds and 22-bit weights, tap-major."""
     from layoutdetr_amd.training.dataset_layoutganpp import resample_coeffs
     from oracle import resample_ref
     for n_in, n_out in sorted({(c['W'], c['out_w']) for c in R.RESIZE_CASES} | {(c['H'], c['out_h']) for c in R.RESIZE_CASES}):

@@ -95,12 +95,13 @@ def _degenerate(rng, B, N):
     return bb, va.astype(np.uint8), rng.randint(0, 5, (B, N))
 
 
-@pytest.mark.parametrize('W,H,S,over', [(50, 30, 16, False), (300, 200, 64, True), (40, 600, 64, False), (1200, 628, 128, False), (640, 640, 64, True)])
+@pytest.mark.parametrize('W,H,S,over', [(50, 30, 16, False), (300, 200, 64, True), (40, 600, 64, False), (1200, 628, 128, False), (640, 640, 64, True),
+                                         (64, 41, 64, True), (41, 64, 64, True)])
 def test_own_rules_for_degenerate_boxes_equal_the_restatement(dev, fx, W, H, S, over):
     """Boxes under 3 pixels, zero size, NaN, infinities, coordinates beyond the int32 range, negative extents, 16 slots -- where Pillow's outline
     path differs between versions or rejects the input, the rule of DESIGN.md section 13 is the definition.  The page sizes take the kernel
-    through one and several bands per cell, several source-row chunks per band, a skipped vertical pass never (see the fixture's 16 x 16 case)
-    and both letterbox directions."""
+    through one and several bands per cell, several source-row chunks per band, both letterbox directions, and one pass skipped while the
+    other runs: 64 x 41 -> a 64 x 40 cell (no horizontal pass), 41 x 64 -> 40 x 64 (no vertical pass); the fixture's 16 x 16 case skips both."""
     rng = np.random.RandomState(W + S)
     B, N = 5, 16
     bb, va, la = _degenerate(rng, B, N)
