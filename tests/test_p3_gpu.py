@@ -139,7 +139,7 @@ FWD_CASES = [
     (3, 16, 16, 128, 256, 1, 2, 0, True),    # strided 1x1 (downsample)
     (4, 32, 32, 128, 128, 3, 1, 1, True),    # patch kernel 8 x 16
     (3, 16, 32, 64, 96, 3, 1, 1, True),      # non-square image on the patch kernel
-    (2, 4, 4, 512, 64, 3, 1, 1, True),       # 4 x 4 images: many images per tile
+    (2, 4, 4, 512, 64, 3, 1, 1, True),       # 4 x 4 images: eight patches per tile would need 18 halo groups (> 13), so the gather kernel
     (16, 8, 8, 512, 512, 3, 1, 1, True),     # split-K (few tiles, long reduction)
     (16, 16, 16, 1024, 256, 1, 1, 0, True),  # split-K 1x1
     (5, 12, 20, 96, 40, 3, 1, 1, True),      # nothing a power of two
