@@ -37,8 +37,11 @@
  *   ldetr_png_scan, ldetr_png_decode_u8
  *                                 PIL.Image.open + np.array of a page PNG written with compress_level=0: dataset_tool.py:325-363,
  *                                 training/dataset_layoutganpp.py:329-340
- *   ldetr_png_encode_bound, ldetr_png_encode_u8
+ *   ldetr_png_encode_bound, ldetr_png_index_bytes, ldetr_png_encode_u8
  *                                 the PNG encoder behind the snapshot grids' save: util.py:141, 231, 325
+ *   ldetr_png_scan_packed, ldetr_png_inflate_u8
+ *                                 PIL.Image.open + np.array of a page PNG the encoder wrote with its index (compressed blocks):
+ *                                 training/dataset_layoutganpp.py:329-340
  *   ldetr_resample_coeffs_filter, ldetr_layout_raster_cell_size, ldetr_layout_raster_u8
  *                                 the snapshot image grids: util.py:85-141 (convert_layout_to_image, save_image)
  *   ldetr_patch_resize_u8, ldetr_image_raster_u8
@@ -600,7 +603,7 @@ typedef struct ldetr_png_encode_args {
     int H, W;
     int blocks;                   /* 0 the smallest per segment, 1 stored, 2 fixed Huffman, 3 dynamic Huffman */
     int filter;                   /* -1 chosen per row, 0 .. 4 that type on every row */
-    int reserved;
+    int reserved;                 /* bit 0: write the ldIX index chunk (below); every other bit 0 */
     const uint8_t* src;           /* device [H][W][3], contiguous */
     uint8_t* out;                 /* device: the file */
     int64_t out_capacity;
@@ -612,6 +615,60 @@ typedef struct ldetr_png_encode_args {
 } ldetr_png_encode_args;
 int ldetr_png_encode_bound(int H, int W, int64_t* out_bytes, int64_t* workspace_bytes);
 int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream);
+/* The index chunk.  With bit 0 of `reserved` set, ldetr_png_encode_u8 writes one ancillary chunk of type ldIX (private, unsafe to
+ * copy) in front of the first IDAT; every other byte of the file is what it is without the bit, at a file offset that much higher.  Payload, big-endian:
+ * u32 version = 1, u32 segment bytes (65536), u32 sub-block bytes (512), H bytes = the filter type of every row, then per segment in order
+ * ceil(segment bytes / 512) u32 entries = the bit offset, from the first data byte of that segment's IDAT chunk (the zlib header counts for segment 0), at
+ * which the first token of the sub-block starts; the entries of a stored segment are 0.  No token crosses a sub-block.
+ * ldetr_png_index_bytes (HOST): *bytes = what the chunk adds, rounded up to 16: with the bit set, out_capacity must be at least
+ * ldetr_png_encode_bound's out_bytes + *bytes and workspace_bytes at least its workspace_bytes + *bytes. */
+int ldetr_png_index_bytes(int H, int W, int64_t* bytes);
+
+/* Indexed page PNGs decoded on the device (csrc/png_inflate.hip, csrc/png_inflate_kernel.hpp).
+ * ldetr_png_scan_packed (HOST memory, no GPU work) accepts exactly the files ldetr_png_encode_u8 writes with its index: 8-bit RGB, non-interlaced, at most
+ * 4096 x 32768; one ldIX chunk (version 1, 65536, 512) in front of the first IDAT; IDAT i holds segment i of the filtered scanline stream, either in the
+ * stored form or as ONE fixed or dynamic block (code lengths as flat 4-bit codes) followed by the empty stored block; the zlib header in the first chunk,
+ * the Adler-32 behind the last.  Outputs: width, height; segments [k][4] = (offset of the chunk's data in the file, its bytes, kind 0 stored / 1 fixed /
+ * 2 dynamic, number of the segment's first index entry); *index_offset = offset of the ldIX chunk's data; row_starts by the rule of ldetr_png_scan, taken
+ * from the index's filter bytes.  The capacity protocol is ldetr_png_scan's.  Returns 0, LDETR_PNG_NOT_ELIGIBLE (well-formed but different: no index,
+ * another version, a foreign zlib stream such as Pillow's) or LDETR_PNG_MALFORMED (broken framing; an ldIX chunk of the wrong length; a filter byte > 4;
+ * entries of a compressed segment that do not start right behind the block header, do not increase strictly or leave the chunk).
+ * ldetr_png_inflate_u8: n files of ONE page size -> dst [n][H][W][3], at most two launches: png_inflate_kernel (one workgroup per page and segment,
+ * one lane per sub-block) writes scratch [n][H][1 + 3 W], then the unfilter of ldetr_png_decode_u8.  The HOST tables are validated before any launch.
+ * status (device int32 [n], ZERO before the call) receives per page the OR of the LDETR_PNG_INFLATE_* bits of a workgroup that found an error; the
+ * kernels clamp every index, so a corrupt file gives a status and wrong pixels, never an access outside the buffers.  Checksums are not checked. */
+#define LDETR_PNG_INFLATE_CODE 1       /* an invalid Huffman code, code-length set or block header */
+#define LDETR_PNG_INFLATE_COUNT 2      /* a sub-block did not yield its byte count exactly or did not end at the next index entry */
+#define LDETR_PNG_INFLATE_HEADER 4     /* the block header did not end at index entry 0 */
+#define LDETR_PNG_INFLATE_DISTANCE 8   /* a distance before the segment start */
+#define LDETR_PNG_INFLATE_TRAILER 16   /* no end-of-block code or no empty stored block up to the end of the chunk */
+#define LDETR_PNG_INFLATE_FILTER 32    /* a filter byte of the stream differs from the index */
+#define LDETR_PNG_INFLATE_STUCK 64     /* matches left unresolved */
+#define LDETR_PNG_INFLATE_TABLE 128    /* a device table entry that leaves its file */
+typedef struct ldetr_png_inflate_args {
+    int struct_bytes;             /* sizeof(ldetr_png_inflate_args) as the caller sees it */
+    int n, H, W;
+    int phases;                   /* 1 inflate only, 2 unfilter only (scratch already inflated), 3 both */
+    int reserved;                 /* 0 */
+    const uint8_t* files;         /* device: the files, concatenated, each at a multiple of 16 bytes; 16-byte aligned */
+    int64_t files_bytes;          /* a multiple of 16 (pad the buffer) */
+    const int64_t* file_off;      /* HOST [n + 1] */
+    const int64_t* file_off_dev;  /* device: the same */
+    const int64_t* segments;      /* HOST [n][ceil(H (1 + 3 W) / 65536)][4]: ldetr_png_scan_packed's rows, page after page */
+    const int64_t* segments_dev;  /* device: the same */
+    const int64_t* index_off;     /* HOST [n]: ldetr_png_scan_packed's index_offset */
+    const int64_t* index_off_dev; /* device: the same */
+    const int32_t* jobs;          /* HOST [n_jobs][3] = (page, first row, end row), pages in order */
+    const int32_t* jobs_dev;      /* device: the same */
+    int64_t n_jobs;
+    uint8_t* scratch;             /* device, 16-byte aligned */
+    int64_t scratch_bytes;        /* a multiple of 16, >= n * H * (1 + 3 W) */
+    uint8_t* dst;                 /* device [n][H][W][3], 4-byte aligned */
+    int32_t* status;              /* device [n], zero before the call */
+} ldetr_png_inflate_args;
+int ldetr_png_scan_packed(const uint8_t* file, int64_t file_bytes, int* width, int* height, int64_t* segments, int64_t segments_capacity, int64_t* segments_count,
+                          int64_t* index_offset, int32_t* row_starts, int64_t row_starts_capacity, int64_t* row_starts_count);
+int ldetr_png_inflate_u8(const ldetr_png_inflate_args* a, void* stream);
 
 /* Batched linear-sum-assignment (Hungarian / shortest augmenting path) on device.
  * cost: [batch][n][n] float64 row-major; maximize != 0 negates the costs first;

@@ -117,6 +117,15 @@ class PngEncodeArgs(Structure):
                 ('workspace', c_void_p), ('workspace_bytes', c_int64), ('seg_table', c_void_p), ('seg_table_rows', c_int64)]
 
 
+class PngInflateArgs(Structure):
+    """ldetr_png_inflate_args."""
+    _fields_ = [('struct_bytes', c_int), ('n', c_int), ('H', c_int), ('W', c_int), ('phases', c_int), ('reserved', c_int),
+                ('files', c_void_p), ('files_bytes', c_int64), ('file_off', c_void_p), ('file_off_dev', c_void_p),
+                ('segments', c_void_p), ('segments_dev', c_void_p), ('index_off', c_void_p), ('index_off_dev', c_void_p),
+                ('jobs', c_void_p), ('jobs_dev', c_void_p), ('n_jobs', c_int64),
+                ('scratch', c_void_p), ('scratch_bytes', c_int64), ('dst', c_void_p), ('status', c_void_p)]
+
+
 _P = c_void_p
 _I = c_int
 _L = c_int64
@@ -211,6 +220,9 @@ SIGNATURES = {
     'ldetr_png_decode_u8': [_P, _P],
     'ldetr_png_encode_bound': [_I, _I, _P, _P],
     'ldetr_png_encode_u8': [_P, _P],
+    'ldetr_png_index_bytes': [_I, _I, _P],
+    'ldetr_png_scan_packed': [_P, _L, _P, _P, _P, _L, _P, _P, _P, _L, _P],
+    'ldetr_png_inflate_u8': [_P, _P],
 }
 
 _lib = None

@@ -34,12 +34,10 @@
 
 #include "ldetr_common.hpp"
 #include "../../include/ldetr_hip.h"
+#include "png_pages.hpp"
 
 namespace ldetr {
 
-constexpr int PNG_MAX_W = 4096;               // the hand-off row is 3 W bytes of LDS
-constexpr int PNG_MAX_H = 32768;
-constexpr int PNG_MIN_RANGE = 64;             // rows: an independent row range is at least one band
 constexpr int PNG_WAVES = 4;
 constexpr int PNG_THREADS = PNG_WAVES * 64;
 constexpr int PNG_CHUNK = 64;                 // steps (pixels) per chunk
@@ -76,11 +74,6 @@ struct IdatCursor {
         return n;
     }
 };
-
-static inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
-#define PNG_MALFORMED(...) do { set_error(__VA_ARGS__); return LDETR_PNG_MALFORMED; } while (0)
-#define PNG_NOT_ELIGIBLE(...) do { set_error(__VA_ARGS__); return LDETR_PNG_NOT_ELIGIBLE; } while (0)
 
 }  // namespace ldetr
 
@@ -186,17 +179,6 @@ extern "C" int ldetr_png_scan(const uint8_t* file, int64_t file_bytes, int* widt
 // device
 
 namespace ldetr {
-
-struct PngParams {
-    const uint8_t* files; long files_bytes;        // files_bytes a multiple of 16
-    const int64_t* file_off;                       // device [n + 1]
-    const int64_t* seg;                            // device [k][4] = (page, offset in file, offset in stream, length)
-    long k;
-    const int32_t* jobs;                           // device [j][3] = (page, first row, end row)
-    uint8_t* stream; long stream_bytes;            // [n][H][1 + 3 W], stream_bytes a multiple of 16 >= n * H * (1 + 3 W)
-    uint8_t* dst;                                  // [n][H][W][3]
-    int n, H, W;
-};
 
 __device__ __forceinline__ long clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -395,6 +377,36 @@ __global__ void __launch_bounds__(PNG_THREADS) png_unfilter_kernel(PngParams p) 
     }
 }
 
+// what ldetr_png_decode_u8 and ldetr_png_inflate_u8 (png_inflate.hip) share: the checks of the host tables both take, and the unfilter launch
+int png_check_file_offsets(const char* who, int n, const int64_t* file_off, int64_t files_bytes) {
+    for (int i = 0; i <= n; i++) {
+        const int64_t o = file_off[i];
+        LDETR_CHECK(o >= 0 && o <= files_bytes && (i == 0 || o >= file_off[i - 1]), "%s: file offset table: entry %d = %ld", who, i, (long)o);
+    }
+    return LDETR_OK;
+}
+
+// the row ranges of a page tile [0, H) in order
+int png_check_jobs(const char* who, int n, int H, const int32_t* jobs, int64_t n_jobs) {
+    int64_t page = 0, run = 0;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        const int32_t* q = jobs + 3 * j;
+        if (q[0] != page) {
+            LDETR_CHECK(q[0] == page + 1 && run == H, "%s: the row ranges of page %ld do not tile its %d rows", who, (long)page, H);
+            page = q[0]; run = 0;
+        }
+        LDETR_CHECK(q[0] < n && q[1] == run && q[2] > q[1] && q[2] <= H, "%s: row range %ld = (%d, %d, %d) does not continue page %ld at row %ld", who, (long)j, q[0], q[1], q[2], (long)page, (long)run);
+        run = q[2];
+    }
+    LDETR_CHECK(page == n - 1 && run == H, "%s: the row ranges of page %ld do not tile its %d rows", who, (long)page, H);
+    return LDETR_OK;
+}
+
+int png_launch_unfilter(const PngParams& p, int64_t n_jobs, hipStream_t st, const char* what) {
+    hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n_jobs), PNG_THREADS, 0, st, p);
+    return check_launch(what);
+}
+
 }  // namespace ldetr
 
 extern "C" int ldetr_png_decode_u8(const ldetr_png_decode_args* a, void* stream) {
@@ -412,10 +424,8 @@ extern "C" int ldetr_png_decode_u8(const ldetr_png_decode_args* a, void* stream)
                 (long)need, (long)a->scratch_bytes);
     LDETR_CHECK(((uintptr_t)a->dst & 3) == 0, "png_decode: dst must be 4-byte aligned");
     LDETR_CHECK(a->n_segments >= 1 && a->n_jobs >= n && a->n_jobs <= (int64_t)n * PNG_MAX_H, "png_decode: %ld segments, %ld row ranges for %d pages", (long)a->n_segments, (long)a->n_jobs, n);
-    for (int i = 0; i <= n; i++) {
-        const int64_t o = a->file_off[i];
-        LDETR_CHECK(o >= 0 && o <= a->files_bytes && (i == 0 || o >= a->file_off[i - 1]), "png_decode: file offset table: entry %d = %ld", i, (long)o);
-    }
+    int rc = png_check_file_offsets("png_decode", n, a->file_off, a->files_bytes);
+    if (rc) return rc;
     // every segment inside its file; the stream offsets of a page tile [0, S) in order
     int64_t page = 0, run = 0;
     for (int64_t s = 0; s < a->n_segments; s++) {
@@ -432,30 +442,19 @@ extern "C" int ldetr_png_decode_u8(const ldetr_png_decode_args* a, void* stream)
         run += q[3];
     }
     LDETR_CHECK(page == n - 1 && run == S, "png_decode: the segments of page %ld do not tile its %ld stream bytes (they end at %ld)", (long)page, (long)S, (long)run);
-    // the row ranges of a page tile [0, H) in order
-    page = 0; run = 0;
-    for (int64_t j = 0; j < a->n_jobs; j++) {
-        const int32_t* q = a->jobs + 3 * j;
-        if (q[0] != page) {
-            LDETR_CHECK(q[0] == page + 1 && run == H, "png_decode: the row ranges of page %ld do not tile its %d rows", (long)page, H);
-            page = q[0]; run = 0;
-        }
-        LDETR_CHECK(q[0] < n && q[1] == run && q[2] > q[1] && q[2] <= H, "png_decode: row range %ld = (%d, %d, %d) does not continue page %ld at row %ld", (long)j, q[0], q[1], q[2], (long)page, (long)run);
-        run = q[2];
-    }
-    LDETR_CHECK(page == n - 1 && run == H, "png_decode: the row ranges of page %ld do not tile its %d rows", (long)page, H);
+    rc = png_check_jobs("png_decode", n, H, a->jobs, a->n_jobs);
+    if (rc) return rc;
     PngParams p;
     p.files = a->files; p.files_bytes = a->files_bytes; p.file_off = a->file_off_dev; p.seg = a->segments_dev; p.k = a->n_segments; p.jobs = a->jobs_dev;
     p.stream = a->scratch; p.stream_bytes = a->scratch_bytes; p.dst = a->dst; p.n = n; p.H = H; p.W = W;
     hipStream_t st = (hipStream_t)stream;
     if (a->phases & 1) {
         hipLaunchKernelGGL(png_gather_kernel, dim3((unsigned)std::min<int64_t>(a->n_segments, 8192)), PNG_GATHER_THREADS, 0, st, p);
-        const int rc = check_launch("png_decode (gather)");
+        rc = check_launch("png_decode (gather)");
         if (rc) return rc;
     }
     if (a->phases & 2) {
-        hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)a->n_jobs), PNG_THREADS, 0, st, p);
-        return check_launch("png_decode (unfilter)");
+        return png_launch_unfilter(p, a->n_jobs, st, "png_decode (unfilter)");
     }
     return LDETR_OK;
 }

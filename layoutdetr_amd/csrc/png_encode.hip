@@ -19,6 +19,10 @@
 //      workgroup adds them up for itself), the payload is copied there and its CRC-32 computed from per-lane slices joined with zlib's crc32_combine
 //      arithmetic (x^(8 n) modulo the CRC polynomial).  The first workgroup writes the signature and IHDR, the last one joins the Adler-32 partial
 //      sums, appends the Adler-32 to its chunk, writes IEND and the total length.
+// With an index requested (bit 0 of ldetr_png_encode_args.reserved) the file carries one more chunk, ldIX, in front of the first IDAT:
+// (a) writes the filter type of every row and (b) the bit offset of every sub-block's first token (what its scan computes anyway) into the chunk's payload in the
+// workspace, and (c) runs one more workgroup that frames it like a segment's chunk while the others start that much later in the file.  Without the bit
+// not one byte of the file changes.
 // The kernels are written as phases of "every thread does this" separated by workgroup barriers (PNG_EACH_THREAD); the same source runs a phase as a
 // loop over the thread index when compiled for the host, which is how the encoder is checked against zlib without a GPU.
 // Every size the assemble kernel reads from the segment table is clamped to the slot and to the output buffer before it is used.
@@ -70,9 +74,15 @@ struct PngEncParams {
     int64_t* user_table;                      // optional [nseg][4]
     int ncand;
     int cand[PE_MAXC];                        // ascending
+    uint8_t* index;                           // workspace, or null: the payload of the ldIX chunk (version, PE_SEG, PE_SUB | filter type [H] | bit offsets, big-endian)
+    long index_bytes;                         // its length; the chunk takes 12 more bytes of the file, in front of the first IDAT
 };
 
 PNG_HD long png_clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+PNG_HD void png_index_be32(const PngEncParams& p, long at, unsigned v) {
+    if (at < 0 || at + 4 > p.index_bytes) return;
+    p.index[at] = (uint8_t)(v >> 24); p.index[at + 1] = (uint8_t)(v >> 16); p.index[at + 2] = (uint8_t)(v >> 8); p.index[at + 3] = (uint8_t)v;
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------
 // (a) filters.  Arithmetic as png_recon of png_decode.hip undoes it.
@@ -121,6 +131,10 @@ __host__ __device__ inline void png_filter_row(PngFilterShared& S, const PngEncP
             if (S.sum[4] < best) { best = S.sum[4]; t = 4; }
         }
         if (tid == 0) dst[0] = (uint8_t)t;
+        if (tid == 0 && p.index) {
+            if (12 + y < p.index_bytes) p.index[12 + y] = (uint8_t)t;
+            if (y == 0) { png_index_be32(p, 0, 1u); png_index_be32(p, 4, (unsigned)PE_SEG); png_index_be32(p, 8, (unsigned)PE_SUB); }
+        }
         for (long i = tid; i < n; i += PE_FILTER_THREADS) {
             const int x = cur[i], a = i >= 3 ? cur[i - 3] : 0, b = up ? up[i] : 0, c = (up && i >= 3) ? up[i - 3] : 0;
             dst[1 + i] = (uint8_t)png_residual(t, x, a, b, c);
@@ -422,6 +436,7 @@ __host__ __device__ inline void png_deflate_segment(PngDeflateShared& S, const P
                 h[1] = (uint8_t)(len & 255); h[2] = (uint8_t)(len >> 8); h[3] = (uint8_t)(~len & 255); h[4] = (uint8_t)((~len >> 8) & 255);
             }
             for (int j = tid; j < n; j += PE_THREADS) z[j + 5 * (j / 65535 + 1)] = S.data[j];
+            if (p.index && tid < nsub) png_index_be32(p, 12 + p.H + 4 * (s * PE_NSUB + tid), 0u);
         }
         return;
     }
@@ -457,6 +472,7 @@ __host__ __device__ inline void png_deflate_segment(PngDeflateShared& S, const P
         for (int sb = tid; sb < nsub; sb += PE_THREADS) {
             PngBitWriter w;
             w.base = z; w.cap = zcap; w.acc = 0ull; w.lim = 0x7fffffffffffffffL;
+            if (p.index) png_index_be32(p, 12 + p.H + 4 * (s * PE_NSUB + sb), S.off[sb] + 8u * (unsigned)zoff);
             int i = sb * PE_SUB;
             const int end = i + PE_SUB < n ? i + PE_SUB : n;
             if (sb == 0) {
@@ -535,9 +551,11 @@ PNG_HD unsigned png_crc_bytes(const PngAsmShared& S, const uint8_t* b, int n) {
 PNG_HD void png_out(const PngEncParams& p, long at, unsigned v) { if (at >= 0 && at < p.out_cap) p.out[at] = (uint8_t)v; }
 PNG_HD void png_out_be32(const PngEncParams& p, long at, unsigned v) { png_out(p, at, v >> 24); png_out(p, at + 1, (v >> 16) & 255u); png_out(p, at + 2, (v >> 8) & 255u); png_out(p, at + 3, v & 255u); }
 
+// s == p.nseg (launched only with an index): the ldIX chunk, framed like a segment's IDAT
 __host__ __device__ inline void png_assemble_segment(PngAsmShared& S, const PngEncParams& p, long s) {
-    const bool last_seg = s == p.nseg - 1;
-    const uint8_t* slot = p.slots + s * PE_SLOT;
+    const bool last_seg = s == p.nseg - 1, is_index = s == p.nseg;
+    const uint8_t* slot = is_index ? p.index : p.slots + s * PE_SLOT;
+    const long index_chunk = p.index ? 12 + p.index_bytes : 0;
     PNG_EACH_THREAD(tid, PE_ASM_THREADS) {
         unsigned c = (unsigned)tid;
         for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ PE_POLY : c >> 1;
@@ -565,9 +583,13 @@ __host__ __device__ inline void png_assemble_segment(PngAsmShared& S, const PngE
     }
     PNG_EACH_THREAD(tid, PE_ASM_THREADS) {
         if (tid == 0) {
-            S.off = PE_FILE_HEAD + (long)S.sum_off;
-            S.plen = png_clampl(p.meta[s * PE_META + 3], 12, 12 + PE_SLOT + 4) - 12 - (last_seg ? 4 : 0);     // payload bytes that sit in the slot
-            S.plen = png_clampl(S.plen, 0, PE_SLOT);
+            S.off = is_index ? PE_FILE_HEAD : PE_FILE_HEAD + index_chunk + (long)S.sum_off;
+            if (is_index) {
+                S.plen = p.index_bytes;
+            } else {
+                S.plen = png_clampl(p.meta[s * PE_META + 3], 12, 12 + PE_SLOT + 4) - 12 - (last_seg ? 4 : 0);     // payload bytes that sit in the slot
+                S.plen = png_clampl(S.plen, 0, PE_SLOT);
+            }
             const unsigned A = (unsigned)((1ull + S.ad_a) % PE_ADLER), B = (unsigned)(((unsigned long long)p.total + S.ad_b) % PE_ADLER);
             S.adler = (B << 16) | A;
         }
@@ -582,7 +604,7 @@ __host__ __device__ inline void png_assemble_segment(PngAsmShared& S, const PngE
             for (int k = tid; k < len; k += PE_ASM_THREADS) {
                 const long q = p0 + k;
                 unsigned v;
-                if (q < 4) v = q == 0 ? 'I' : (q == 1 ? 'D' : (q == 2 ? 'A' : 'T'));
+                if (q < 4) v = is_index ? (q == 0 ? 'l' : (q == 1 ? 'd' : (q == 2 ? 'I' : 'X'))) : (q == 0 ? 'I' : (q == 1 ? 'D' : (q == 2 ? 'A' : 'T')));
                 else if (q < 4 + plen) v = slot[q - 4];
                 else v = (adler >> (8 * (3 - (q - 4 - plen)))) & 255u;
                 S.stage[k] = (uint8_t)v;
@@ -611,7 +633,7 @@ __host__ __device__ inline void png_assemble_segment(PngAsmShared& S, const PngE
         if (tid == 0) {
             png_out_be32(p, off, (unsigned)(body - 4));
             png_out_be32(p, off + 4 + body, S.crc_total);
-            if (p.user_table) {
+            if (p.user_table && !is_index) {
                 const int64_t* m = p.meta + s * PE_META;
                 int64_t* u = p.user_table + 4 * s;
                 u[0] = m[0]; u[1] = m[1]; u[2] = m[2]; u[3] = 12 + body - 4;
@@ -658,7 +680,7 @@ __global__ void __launch_bounds__(PE_ASM_THREADS) png_enc_assemble_kernel(PngEnc
 static inline int64_t pe_round16(int64_t v) { return (v + 15) / 16 * 16; }
 
 // workspace layout: stream | segment table | slots, each 16-byte aligned
-struct PngEncLayout { int64_t total, nseg, stream_bytes, meta_off, slots_off, workspace, bound; };
+struct PngEncLayout { int64_t total, nseg, stream_bytes, meta_off, slots_off, workspace, bound, index_bytes; };
 
 static inline PngEncLayout png_enc_layout(int H, int W) {
     PngEncLayout l;
@@ -670,6 +692,7 @@ static inline PngEncLayout png_enc_layout(int H, int W) {
     l.workspace = l.slots_off + l.nseg * PE_SLOT;
     const int64_t tail = l.total - (l.nseg - 1) * PE_SEG;
     l.bound = PE_FILE_HEAD + 2 + (l.nseg - 1) * (12 + png_stored_bytes(PE_SEG)) + 12 + png_stored_bytes(tail) + 4 + 12;
+    l.index_bytes = 12 + H + 4 * ((l.nseg - 1) * PE_NSUB + (tail + PE_SUB - 1) / PE_SUB);     // the ldIX payload, behind the slots in the workspace
     return l;
 }
 
@@ -704,6 +727,13 @@ extern "C" int ldetr_png_encode_bound(int H, int W, int64_t* out_bytes, int64_t*
     return LDETR_OK;
 }
 
+extern "C" int ldetr_png_index_bytes(int H, int W, int64_t* bytes) {
+    LDETR_CHECK(W >= 1 && W <= PE_MAX_DIM && H >= 1 && H <= PE_MAX_DIM, "png_index_bytes: grid %d x %d outside [1, %d] x [1, %d]", W, H, PE_MAX_DIM, PE_MAX_DIM);
+    LDETR_CHECK(bytes, "png_index_bytes: null pointer");
+    *bytes = pe_round16(12 + png_enc_layout(H, W).index_bytes);
+    return LDETR_OK;
+}
+
 extern "C" int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream) {
     LDETR_CHECK_BLOCK(a, ldetr_png_encode_args, "png_encode");
     const int H = a->H, W = a->W;
@@ -711,8 +741,15 @@ extern "C" int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream)
     LDETR_CHECK(a->blocks >= 0 && a->blocks <= 3, "png_encode: blocks %d (0 auto, 1 stored, 2 fixed, 3 dynamic)", a->blocks);
     LDETR_CHECK(a->filter >= -1 && a->filter <= 4, "png_encode: filter %d (-1 auto, 0 .. 4)", a->filter);
     LDETR_CHECK(a->src && a->out && a->total_bytes && a->workspace, "png_encode: null pointer");
-    const PngEncLayout l = png_enc_layout(H, W);
-    LDETR_CHECK(a->out_capacity >= l.bound, "png_encode: the output buffer holds %ld bytes, a %d x %d grid needs %ld (ldetr_png_encode_bound)", (long)a->out_capacity, W, H, (long)l.bound);
+    LDETR_CHECK((a->reserved & ~1) == 0, "png_encode: reserved %d (bit 0: write the ldIX index chunk)", a->reserved);
+    PngEncLayout l = png_enc_layout(H, W);
+    const bool index = a->reserved & 1;
+    if (index) {                                                                                                    // both buffers grow by ldetr_png_index_bytes
+        const int64_t extra = pe_round16(12 + l.index_bytes);
+        l.bound += extra; l.workspace += extra;
+    }
+    LDETR_CHECK(a->out_capacity >= l.bound, "png_encode: the output buffer holds %ld bytes, a %d x %d grid needs %ld (ldetr_png_encode_bound%s)", (long)a->out_capacity, W, H, (long)l.bound,
+                index ? " + ldetr_png_index_bytes" : "");
     LDETR_CHECK(((uintptr_t)a->workspace & 15) == 0 && a->workspace_bytes >= l.workspace, "png_encode: the workspace must be 16-byte aligned and hold %ld bytes (got %ld)", (long)l.workspace,
                 (long)a->workspace_bytes);
     LDETR_CHECK(!a->seg_table || a->seg_table_rows >= l.nseg, "png_encode: the segment table holds %ld rows, %ld needed", (long)a->seg_table_rows, (long)l.nseg);
@@ -720,6 +757,7 @@ extern "C" int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream)
     p.src = a->src; p.H = H; p.W = W; p.mode = a->blocks; p.filter = a->filter;
     p.stream = a->workspace; p.meta = reinterpret_cast<int64_t*>(a->workspace + l.meta_off); p.slots = a->workspace + l.slots_off;
     p.nseg = l.nseg; p.total = l.total; p.out = a->out; p.out_cap = a->out_capacity; p.out_total = a->total_bytes; p.user_table = a->seg_table;
+    p.index = index ? a->workspace + l.slots_off + l.nseg * PE_SLOT : nullptr; p.index_bytes = index ? l.index_bytes : 0;
     p.ncand = png_enc_candidates(W, p.cand);
     for (int i = p.ncand; i < PE_MAXC; i++) p.cand[i] = 0x7fffffff;
     {
@@ -734,6 +772,6 @@ extern "C" int ldetr_png_encode_u8(const ldetr_png_encode_args* a, void* stream)
     hipLaunchKernelGGL(png_enc_deflate_kernel, dim3((unsigned)l.nseg), PE_THREADS, sizeof(PngDeflateShared), st, p);
     rc = check_launch("png_encode (deflate)");
     if (rc) return rc;
-    hipLaunchKernelGGL(png_enc_assemble_kernel, dim3((unsigned)l.nseg), PE_ASM_THREADS, sizeof(PngAsmShared), st, p);
+    hipLaunchKernelGGL(png_enc_assemble_kernel, dim3((unsigned)(l.nseg + (index ? 1 : 0))), PE_ASM_THREADS, sizeof(PngAsmShared), st, p);
     return check_launch("png_encode (assemble)");
 }

@@ -172,7 +172,8 @@ DATASET_MODE_ENV = 'LDETR_DATASET_MODE'       # read by training/dataset_layoutg
 def parse_options(argv, environ):
     """The options in front of the script: each sets the environment variable the training code reads; returns what is left of argv.
     --image-snapshot-kinds: which snapshot kinds training_loop writes (training/snapshot_images.py);
-    --dataset-mode: 'device' (Pillow decodes the page on the host) or 'raw' (the page's PNG bytes go to the GPU and are decoded there);
+    --dataset-mode: 'device' (Pillow decodes the page on the host), 'raw' (the PNG bytes of a stored-block page go to the GPU and are decoded there) or
+    'packed' (as 'raw', and pages repacked with their index by layoutdetr_amd.repack_dataset are inflated there too);
     --snapshot-png: 'pillow' (the snapshot grid is copied to the host and Pillow encodes it) or 'device' (render.encode_png: the GPU encodes, only the
     file's bytes are copied)."""
     argv = list(argv)
@@ -187,8 +188,8 @@ def parse_options(argv, environ):
                 raise SystemExit(f"--snapshot-png: 'pillow' or 'device' (got {value!r})")
             environ[SNAPSHOT_PNG_ENV] = value
         else:
-            if value not in ('device', 'raw'):
-                raise SystemExit(f"--dataset-mode: 'device' or 'raw' (got {value!r})")
+            if value not in ('device', 'raw', 'packed'):
+                raise SystemExit(f"--dataset-mode: 'device', 'raw' or 'packed' (got {value!r})")
             environ[DATASET_MODE_ENV] = value
     return argv
 
@@ -197,7 +198,7 @@ def main(argv):
     import os
     argv = parse_options(argv, os.environ)
     if not argv:
-        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] [--dataset-mode=device|raw] [--snapshot-png=pillow|device] <script.py> [script args...]')
+        raise SystemExit('usage: python -m layoutdetr_amd.dropin [--image-snapshot-kinds=layouts,images,...] [--dataset-mode=device|raw|packed] [--snapshot-png=pillow|device] <script.py> [script args...]')
     sys.path.insert(0, os.path.dirname(os.path.abspath(argv[0])))
     for pkg in ('training', 'torch_utils', 'torch_utils.ops'):     # import the reference's packages first so aliases attach to them
         try:

@@ -308,7 +308,7 @@ class _ItemWalk(object):
         if data_loader_kwargs is None:
             data_loader_kwargs = opts.data_loader_kwargs
         kw = dict(num_workers=0) if data_loader_kwargs is None else dict(data_loader_kwargs)
-        if getattr(dataset, 'mode', None) in ('device', 'raw') and hasattr(dataset, 'collate'):
+        if getattr(dataset, 'mode', None) in ('device', 'raw', 'packed') and hasattr(dataset, 'collate'):
             kw.setdefault('collate_fn', dataset.collate)
         self.loader = torch.utils.data.DataLoader(dataset=dataset, sampler=self.item_subset, batch_size=self.batch_size, **kw)
 

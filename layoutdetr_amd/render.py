@@ -202,12 +202,24 @@ def png_encode_segments(H, W):
     return [(a, min(a + PNG_ENCODE_SEGMENT, total)) for a in range(0, total, PNG_ENCODE_SEGMENT)]
 
 
-def encode_png(grid, blocks='auto', filter='auto', return_stats=False):
+def png_index_bytes(H, W):
+    """What encode_png(index=True) adds to both of png_encode_bound's figures: the ldIX chunk, rounded up to 16 bytes (ldetr_png_index_bytes; host
+    arithmetic only)."""
+    _check_grid_size(H, W)
+    out = ctypes.c_int64(0)
+    _lib.check(_lib.load().ldetr_png_index_bytes(int(H), int(W), ctypes.byref(out)), 'png_index_bytes')
+    return out.value
+
+
+def encode_png(grid, blocks='auto', filter='auto', return_stats=False, index=False):
     """A uint8 [H, W, 3] grid in GPU memory -> the bytes of its PNG file as a host uint8 tensor, encoded on the device (csrc/png_encode.hip, DESIGN.md
     §17): three launches, then one 8-byte copy (the length) and one copy of exactly that many bytes.  blocks: 'auto' takes the smallest of a stored,
     a fixed-Huffman and a dynamic-Huffman block per 64 KiB segment; 'stored' / 'fixed' / 'dynamic' force one type ('stored' gives a file
     dataset_layoutganpp.scan_png finds eligible).  filter: 'auto' picks per row by the minimum sum of absolute residuals, 0..4 force a type.
     return_stats=True: (bytes, stats) with stats['segments'] an int64 [n, 4] array of (first byte, end byte, block type 0 / 1 / 2, chunk bytes).
+    index=True adds the ancillary ldIX chunk in front of the first IDAT (the filter type of every row and the bit offset of every
+    512-byte sub-block's first token), which lets dataset_layoutganpp.scan_png(packed=True) / decode_pages inflate the file on the device; every other
+    byte of the file is the same, and decoders that do not know the chunk skip it.
     There is no CPU path: a CPU tensor raises."""
     core.require_gpu(grid)
     if grid.dtype != torch.uint8 or grid.ndim != 3 or grid.shape[2] != 3:
@@ -221,12 +233,15 @@ def encode_png(grid, blocks='auto', filter='auto', return_stats=False):
     bound, ws_bytes = png_encode_bound(H, W)
     nseg = len(png_encode_segments(H, W))
     cap = bound if _BLOCKS[blocks] < 2 else 64 + nseg * (12 + PNG_ENCODE_SLOT)
+    if index:
+        extra = png_index_bytes(H, W)
+        bound, ws_bytes, cap = bound + extra, ws_bytes + extra, cap + extra
     dev = grid.device
     src = grid.contiguous()
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     small = torch.zeros(1 + 4 * nseg, dtype=torch.int64, device=dev)          # [total length | segment table]
-    a = _lib.PngEncodeArgs(struct_bytes=ctypes.sizeof(_lib.PngEncodeArgs), H=H, W=W, blocks=_BLOCKS[blocks], filter=-1 if filter == 'auto' else int(filter), reserved=0,
+    a = _lib.PngEncodeArgs(struct_bytes=ctypes.sizeof(_lib.PngEncodeArgs), H=H, W=W, blocks=_BLOCKS[blocks], filter=-1 if filter == 'auto' else int(filter), reserved=1 if index else 0,
                            src=src.data_ptr(), out=out.data_ptr(), out_capacity=cap, total_bytes=small.data_ptr(),
                            workspace=ws.data_ptr(), workspace_bytes=ws_bytes, seg_table=small.data_ptr() + 8, seg_table_rows=nseg)
     core.check(core.lib().ldetr_png_encode_u8(ctypes.byref(a), core.stream()), 'png_encode_u8')
@@ -243,9 +258,10 @@ def encode_png(grid, blocks='auto', filter='auto', return_stats=False):
     return data
 
 
-def save_png(grid, path, encoder=None):
+def save_png(grid, path, encoder=None, index=False):
     """Write a uint8 [H, W, 3] grid as a PNG.  encoder 'pillow' (the default): one device-to-host copy of the pixels, then PIL encodes; 'device':
-    encode_png on the GPU, only the file's bytes cross to the host.  None reads the environment variable LDETR_SNAPSHOT_PNG (unset: 'pillow')."""
+    encode_png on the GPU, only the file's bytes cross to the host.  None reads the environment variable LDETR_SNAPSHOT_PNG (unset: 'pillow').
+    index=True (the device encoder only): the file carries the ldIX chunk of encode_png(index=True)."""
     if grid.dtype != torch.uint8 or grid.ndim != 3 or grid.shape[2] != 3:
         raise ValueError('save_png: expected a uint8 [H, W, 3] grid')
     if encoder is None:
@@ -255,8 +271,10 @@ def save_png(grid, path, encoder=None):
             raise ValueError(f"{PNG_ENV} must be 'pillow' or 'device' (got {encoder!r})")
     elif encoder not in ('pillow', 'device'):
         raise ValueError(f"save_png: encoder must be 'pillow', 'device' or None for {PNG_ENV} (got {encoder!r})")
+    if index and encoder != 'device':
+        raise ValueError("save_png: index=True needs encoder='device' (Pillow writes no ldIX chunk)")
     if encoder == 'device':
-        data = encode_png(grid).numpy()
+        data = encode_png(grid, index=index).numpy()
         with open(path, 'wb') as f:
             f.write(memoryview(data))
         return

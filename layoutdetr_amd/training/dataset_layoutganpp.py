@@ -23,6 +23,10 @@ nine slots with a validity mask (`to_dense_batch`, :29-41).
   (compress_level=0) -- and the Pillow-decoded uint8 page, exactly as 'device' produces it, otherwise (a per-item fallback, counted in
   `route_counts`).  `batch_backgrounds_to_device` decodes the raw pages of a batch on the GPU (`decode_pages`, csrc/png_decode.hip: a gather of
   the stored payload + PNG's row filters undone, bit-identical to Pillow) and proceeds as for 'device'.
+* mode='packed' (opt-in; `LDETR_DATASET_MODE=packed`, `--dataset-mode=packed`): as 'raw', and a page whose file carries the encoder's ldIX index
+  (`python -m layoutdetr_amd.repack_dataset`, DESIGN.md §18) also goes out as file bytes and is inflated on the GPU (csrc/png_inflate.hip);
+  everything else is decoded with Pillow.  `route_counts` has a 'packed' key in this mode.  The inflate kernel's per-page status words are checked
+  at the next `batch_backgrounds_to_device` call and at `close()`: no synchronisation point is added to the step.
 * mode='reference': every key of the reference's item, computed on the host exactly as the reference does (PIL decode + Lanczos
   resize, float normalise, transpose) — what `setup_snapshot` (training_loop.py:36-59) needs, and the side that
   tests/golden/dataset.npz (the reference's own `__getitem__` on tests/golden/dataset_tiny.zip) pins.
@@ -123,8 +127,11 @@ def background_to_tensor(pages_u8, background_size, return_u8=False, mean=RGB_ME
 # ---------------------------------------------------------------------------------------------------------------------------------
 # stored-block PNG pages: host scan + device decode (csrc/png_decode.hip)
 
-DATASET_MODES = ('device', 'raw', 'reference')
+DATASET_MODES = ('device', 'raw', 'packed', 'reference')
 PNG_NOT_ELIGIBLE, PNG_MALFORMED = 3, 4                  # include/ldetr_hip.h LDETR_PNG_*
+PNG_INFLATE_ERRORS = {1: 'an invalid Huffman code or block header', 2: 'a sub-block that does not yield its 512 bytes or does not end at the next index entry',
+                      4: 'a block header that does not end at index entry 0', 8: 'a distance before the segment start', 16: 'no end-of-block code or empty stored block',
+                      32: 'a filter byte that differs from the index', 64: 'matches left unresolved', 128: 'a stale segment table'}      # LDETR_PNG_INFLATE_*
 
 
 def default_dataset_mode():
@@ -138,11 +145,16 @@ def default_dataset_mode():
 class RawPage:
     """One eligible page PNG as `scan_png` found it: `data` the file bytes (1-D uint8, numpy or a CPU torch tensor), `width`, `height`,
     `segments` int64 [k, 3] = (offset in file, offset in the filtered scanline stream, length) and `row_starts` int32 [r], the rows at
-    which `decode_pages` starts an independent row range."""
-    __slots__ = ('data', 'width', 'height', 'segments', 'row_starts')
+    which `decode_pages` starts an independent row range.  `kind` is 'stored' (the above) or 'packed': an indexed file of compressed blocks
+    (DESIGN.md §18), whose `packed` = (int64 [k, 4] = (offset of the IDAT data, bytes, block type, first index entry), offset of the ldIX data) replaces
+    `segments` (None then)."""
+    __slots__ = ('data', 'width', 'height', 'segments', 'row_starts', 'kind', 'packed')
 
-    def __init__(self, data, width, height, segments, row_starts):
+    def __init__(self, data, width, height, segments, row_starts, kind='stored', packed=None):
         self.data, self.width, self.height, self.segments, self.row_starts = data, int(width), int(height), segments, row_starts
+        if kind not in ('stored', 'packed') or (kind == 'packed') != (packed is not None):
+            raise ValueError("RawPage: kind is 'stored', or 'packed' with its segment table")
+        self.kind, self.packed = kind, packed
 
     shape = property(lambda self: (self.height, self.width, 3))          # of the decoded page
 
@@ -151,7 +163,7 @@ class RawPage:
 
     def pin_memory(self, device=None):
         """What DataLoader(pin_memory=True) calls on a batch element: the file bytes in page-locked memory, the tables as they are."""
-        return RawPage(self.tensor().pin_memory(), self.width, self.height, self.segments, self.row_starts)
+        return RawPage(self.tensor().pin_memory(), self.width, self.height, self.segments, self.row_starts, self.kind, self.packed)
 
 
 def _verify_png(data):
@@ -171,11 +183,41 @@ def _verify_png(data):
     return b''.join(idat)
 
 
-def scan_png(data, verify=False):
+def _scan_png_packed(arr, verify):
+    """`ldetr_png_scan_packed` on a file the stored scan did not take -> a 'packed' `RawPage`, or None."""
+    from .. import _lib
+    lib = _lib.load()
+    w, h = ctypes.c_int(0), ctypes.c_int(0)
+    k, r, ix = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    src = arr.ctypes.data_as(ctypes.c_void_p)
+
+    def call(seg, rows):
+        rc = lib.ldetr_png_scan_packed(src, arr.size, ctypes.byref(w), ctypes.byref(h), seg.ctypes.data_as(ctypes.c_void_p) if seg is not None else None,
+                                       len(seg) if seg is not None else 0, ctypes.byref(k), ctypes.byref(ix), rows.ctypes.data_as(ctypes.c_void_p) if rows is not None else None,
+                                       len(rows) if rows is not None else 0, ctypes.byref(r))
+        if rc == PNG_MALFORMED:
+            raise ValueError(lib.ldetr_last_error().decode('utf-8', 'replace'))
+        if rc != PNG_NOT_ELIGIBLE:
+            _lib.check(rc, 'png_scan_packed')
+        return rc
+    if call(None, None) == PNG_NOT_ELIGIBLE:
+        return None
+    seg, rows = np.zeros((k.value, 4), np.int64), np.zeros(r.value, np.int32)
+    call(seg, rows)
+    if verify:
+        try:
+            zlib.decompress(_verify_png(arr))                              # (raises on a wrong Adler-32)
+        except zlib.error as e:
+            raise ValueError(f'scan_png: the zlib stream does not check out ({e})')
+    return RawPage(arr, w.value, h.value, None, rows, 'packed', (seg, int(ix.value)))
+
+
+def scan_png(data, verify=False, packed=False):
     """One PNG file (bytes, or a 1-D uint8 array) -> `RawPage` when the device path takes it, None when it is a well-formed PNG that it does
     not take (compressed blocks, interlace, palette, 16-bit, grey / RGBA, ...: the caller decodes those with Pillow); ValueError for a malformed
     file.  Host work only (`ldetr_png_scan`).  verify=True also checks every chunk's CRC-32 and the stream's Adler-32, which Pillow does and the
-    scan does not, and raises ValueError on a mismatch."""
+    scan does not, and raises ValueError on a mismatch.  packed=True: a file the stored scan does not take is offered to `ldetr_png_scan_packed`
+    (the indexed files of `render.encode_png(index=True)`) before None is returned; the RawPage's `kind` tells the two apart."""
     # (bytes are copied once: torch takes writable arrays only; LayoutDataset reads the zip entry straight into an array instead)
     arr = np.frombuffer(data, np.uint8).copy() if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
     from .. import _lib
@@ -194,7 +236,7 @@ def scan_png(data, verify=False):
             _lib.check(rc, 'png_scan')
         return rc
     if call(None, None) == PNG_NOT_ELIGIBLE:
-        return None
+        return _scan_png_packed(arr, verify) if packed else None
     seg, rows = np.zeros((k.value, 3), np.int64), np.zeros(r.value, np.int32)
     call(seg, rows)
     if verify:
@@ -249,9 +291,85 @@ def _decode_group(pages, device, phases=3, state=None):
     return st['dst']
 
 
-def decode_pages(raw_pages, device):
+def _inflate_group(pages, device, phases=3, state=None):
+    """One `ldetr_png_inflate_u8` call: 'packed' RawPages of one size -> (uint8 [n, H, W, 3], int32 [n] status) on `device`.  `state` as in `_decode_group`."""
+    from .. import _lib
+    n, H, W = len(pages), pages[0].height, pages[0].width
+    if state is None or 'files' not in state:
+        off, pos, jobs = [], 0, []
+        for i, p in enumerate(pages):
+            off.append(pos)
+            pos += (int(p.tensor().numel()) + 15) // 16 * 16
+            starts = np.asarray(p.row_starts, np.int32).reshape(-1)
+            jobs.append(np.stack([np.full(len(starts), i, np.int32), starts, np.append(starts[1:], np.int32(p.height))], 1))
+        off = np.asarray(off + [pos], np.int64)
+        seg = np.ascontiguousarray(np.concatenate([np.asarray(p.packed[0], np.int64).reshape(-1, 4) for p in pages], 0))
+        ix = np.asarray([p.packed[1] for p in pages], np.int64)
+        jobs = np.ascontiguousarray(np.concatenate(jobs, 0).astype(np.int32))
+        host = torch.zeros(pos, dtype=torch.uint8, pin_memory=all(p.tensor().is_pinned() for p in pages))
+        for i, p in enumerate(pages):
+            t = p.tensor()
+            host[int(off[i]):int(off[i]) + t.numel()] = t
+        tables = torch.from_numpy(np.concatenate([off.view(np.uint8), seg.reshape(-1).view(np.uint8), ix.view(np.uint8), jobs.reshape(-1).view(np.uint8)]))
+        st = dict(off=off, seg=seg, ix=ix, jobs=jobs, files=host.to(device, non_blocking=True), tables=tables.to(device, non_blocking=True),
+                  scratch=torch.empty((n * H * (1 + 3 * W) + 15) // 16 * 16, dtype=torch.uint8, device=device),
+                  dst=torch.empty((n, H, W, 3), dtype=torch.uint8, device=device), status=torch.zeros(n, dtype=torch.int32, device=device))
+        if state is not None:
+            state.update(st)
+    else:
+        st = state
+    core.require_gpu(st['files'])
+    tp = st['tables'].data_ptr()                                          # [file offsets | segments | index offsets | row ranges], as on the host
+    a = _lib.PngInflateArgs(struct_bytes=ctypes.sizeof(_lib.PngInflateArgs), n=n, H=H, W=W, phases=phases, reserved=0,
+                            files=core.ptr(st['files']), files_bytes=st['files'].numel(),
+                            file_off=st['off'].ctypes.data, file_off_dev=tp,
+                            segments=st['seg'].ctypes.data, segments_dev=tp + st['off'].nbytes,
+                            index_off=st['ix'].ctypes.data, index_off_dev=tp + st['off'].nbytes + st['seg'].nbytes,
+                            jobs=st['jobs'].ctypes.data, jobs_dev=tp + st['off'].nbytes + st['seg'].nbytes + st['ix'].nbytes, n_jobs=len(st['jobs']),
+                            scratch=core.ptr(st['scratch']), scratch_bytes=st['scratch'].numel(), dst=core.ptr(st['dst']), status=core.ptr(st['status']))
+    core.check(core.lib().ldetr_png_inflate_u8(ctypes.byref(a), core.stream()), 'png_inflate_u8')
+    return st['dst'], st['status']
+
+
+class PageStatus(object):
+    """The status words of the 'packed' groups of one `decode_pages` call, on their way to the host: `check()` waits for the copy (not for anything
+    enqueued after it) and raises ValueError naming the first page whose file the inflate kernel found corrupt."""
+
+    def __init__(self):
+        self.parts = []                                                    # (pinned int32 [n], positions in the call's page list)
+        self.event = None
+
+    def add(self, status, positions):
+        host = torch.empty(status.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        self.parts.append((host, list(positions)))
+        self.event = torch.cuda.Event()
+        self.event.record()
+
+    def tensor(self):
+        """int32 [pages of packed groups], in group order."""
+        if self.event is not None:
+            self.event.synchronize()
+        return torch.cat([h for h, _ in self.parts]) if self.parts else torch.zeros(0, dtype=torch.int32)
+
+    def check(self, names=None):
+        if self.event is not None:
+            self.event.synchronize()
+        for host, positions in self.parts:
+            for v, i in zip(host.tolist(), positions):
+                if v:
+                    what = '; '.join(t for b, t in PNG_INFLATE_ERRORS.items() if v & b)
+                    raise ValueError(f'decode_pages: page {names[i] if names else i}: the indexed PNG is corrupt (status {v}: {what})')
+
+
+def decode_pages(raw_pages, device, status=None):
     """`RawPage`s -> the decoded pages in GPU memory, bit-identical to np.array(PIL.Image.open(...)): uint8 [n, H, W, 3] when the pages share
-    a size, else a list of [H, W, 3] tensors in the order given.  One `ldetr_png_decode_u8` call (two launches) per distinct page size.
+    a size, else a list of [H, W, 3] tensors in the order given.  One `ldetr_png_decode_u8` call ('stored' pages) or `ldetr_png_inflate_u8` call
+    ('packed' pages; two launches either way) per distinct kind and page size.  The inflate kernel reports a corrupt file in a status word per page:
+    with status=None the call waits for them and raises ValueError naming the page; pass a `PageStatus` to collect them instead and `check()` it later
+    (`batch_backgrounds_to_device` does, so that the training step gets no synchronisation point).  A page's word is written with plain stores by
+    every workgroup (segment) that found an error, so it holds the bits of ONE of them, not their union: non-zero always means corrupt, but the
+    message may name only some of the faults of a file that has several.
     There is no CPU path: without a GPU device it raises."""
     raw_pages = list(raw_pages)
     if not raw_pages or not all(isinstance(p, RawPage) for p in raw_pages):
@@ -261,15 +379,40 @@ def decode_pages(raw_pages, device):
         raise RuntimeError(f'decode_pages: needs a GPU device (got {device}); layoutdetr_amd has no CPU path')
     groups = {}
     for i, p in enumerate(raw_pages):
-        groups.setdefault((p.height, p.width), []).append(i)
+        groups.setdefault((p.kind, p.height, p.width), []).append(i)
+    collect = PageStatus() if status is None else status
+
+    def run(idx):
+        pages = [raw_pages[i] for i in idx]
+        if pages[0].kind == 'stored':
+            return _decode_group(pages, device)
+        dec, st = _inflate_group(pages, device)
+        collect.add(st, idx)
+        return dec
     if len(groups) == 1:
-        return _decode_group(raw_pages, device)
-    out = [None] * len(raw_pages)
-    for idx in groups.values():
-        dec = _decode_group([raw_pages[i] for i in idx], device)
-        for j, i in enumerate(idx):
-            out[i] = dec[j]
+        out = run(list(range(len(raw_pages))))
+    else:
+        out = [None] * len(raw_pages)
+        for idx in groups.values():
+            dec = run(idx)
+            for j, i in enumerate(idx):
+                out[i] = dec[j]
+    if status is None:
+        collect.check()
     return out
+
+
+# batch_backgrounds_to_device: the PageStatus of the call before.  ONE list per process, not per dataset: the function sees a collated batch, not the
+# dataset it came from, and a training process decodes the pages of one training set.  So the error of a corrupt page surfaces at the next
+# batch_backgrounds_to_device call whichever dataset's batch that is, or when a mode='packed' dataset is closed (datasets of other modes do not look).
+_pending_status = []
+
+
+def check_pending_status():
+    """Raise for a corrupt indexed page the previous `batch_backgrounds_to_device` call decoded (its status words crossed to the host since).
+    Process-wide: see `_pending_status`."""
+    while _pending_status:
+        _pending_status.pop(0).check()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -403,9 +546,11 @@ class LayoutDataset(Dataset):
         if mode is None:
             mode = default_dataset_mode()
         if mode not in DATASET_MODES:
-            raise ValueError("LayoutDataset: mode must be 'device', 'raw' or 'reference'")
+            raise ValueError("LayoutDataset: mode must be 'device', 'raw', 'packed' or 'reference'")
         self.verify_png = bool(verify_png)
         self.route_counts = {'raw': 0, 'decoded': 0}         # mode='raw': items whose page went out as file bytes / was decoded here with Pillow
+        if mode == 'packed':                                 # ... / went out as the bytes of an indexed file of compressed blocks
+            self.route_counts = {'raw': 0, 'packed': 0, 'decoded': 0}
         self._path = path
         self.background_size = background_size
         self.mode = mode
@@ -457,6 +602,13 @@ class LayoutDataset(Dataset):
         return data
 
     def close(self):
+        try:
+            if self.mode == 'packed':                        # the status words of the last batch decoded on the device (no other mode produces any)
+                check_pending_status()
+        finally:
+            self._close_files()
+
+    def _close_files(self):
         try:
             if self._zipfile is not None:
                 self._zipfile.close()
@@ -541,16 +693,16 @@ class LayoutDataset(Dataset):
             out['background'] = page                                                          # uint8 [H, W, 3]; resized + normalised on the GPU
             out['patches'] = np.broadcast_to(np.zeros((), np.float32), (9, 3, 256, 256))      # shape only, never read
             return out
-        if self.mode == 'raw':
+        if self.mode in ('raw', 'packed'):
             data = self._read_entry(base + '_background_orig.png')
-            raw = scan_png(data, verify=self.verify_png)
-            if raw is None:                                                                   # not a stored-block 8-bit RGB file: this item takes the 'device' route
+            raw = scan_png(data, verify=self.verify_png, packed=self.mode == 'packed')
+            if raw is None:                                                                   # neither a stored-block nor (mode='packed') an indexed 8-bit RGB file: this item takes the 'device' route
                 import PIL.Image
                 page = np.array(PIL.Image.open(io.BytesIO(data.tobytes())))
                 if page.ndim != 3 or page.shape[2] != 3:
                     raise ValueError(f'{base}_background_orig.png: expected an RGB page (:334)')
                 raw = page
-            self.route_counts['raw' if isinstance(raw, RawPage) else 'decoded'] += 1
+            self.route_counts[('packed' if raw.kind == 'packed' else 'raw') if isinstance(raw, RawPage) else 'decoded'] += 1
             out['background'] = raw
             out['patches'] = np.broadcast_to(np.zeros((), np.float32), (9, 3, 256, 256))
             return out
@@ -632,6 +784,7 @@ def batch_backgrounds_to_device(background, background_size, device, page_filter
     page_filter ('blur' / 'edge') filters the uint8 pages before the resize; float backgrounds are already resized, so a filter on them raises."""
     if page_filter is not None and page_filter not in PAGE_FILTER_KINDS:
         raise ValueError(f'batch_backgrounds_to_device: page_filter must be None or one of {sorted(PAGE_FILTER_KINDS)} (got {page_filter!r})')
+    check_pending_status()                                                   # mode='packed': what the call before found, by now on the host
     if torch.is_tensor(background):
         if background.dtype != torch.uint8:
             if page_filter is not None:
@@ -639,8 +792,11 @@ def batch_backgrounds_to_device(background, background_size, device, page_filter
             return background.to(device).float()
         return background_to_tensor(background.to(device, non_blocking=True), background_size, page_filter=page_filter)
     raw = [i for i, p in enumerate(background) if isinstance(p, RawPage)]
-    if raw:                                                                  # mode='raw': the file bytes go up, the pages are decoded there
-        dec = decode_pages([background[i] for i in raw], device)
+    if raw:                                                                  # mode='raw' / 'packed': the file bytes go up, the pages are decoded there
+        status = PageStatus()
+        dec = decode_pages([background[i] for i in raw], device, status=status)
+        if status.parts:
+            _pending_status.append(status)
         if len(raw) == len(background) and torch.is_tensor(dec):
             return background_to_tensor(dec, background_size, page_filter=page_filter)
         background = list(background)

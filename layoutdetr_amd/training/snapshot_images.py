@@ -78,12 +78,12 @@ class SnapshotGrid(object):
         self.kinds, self.image_canvas = parse_kinds(kinds), int(image_canvas)
         self.indices = grid_indices(len(dataset), batch_size, random_seed)
         items = [dataset[i] for i in self.indices]
-        collate = dataset.collate if (getattr(dataset, 'mode', None) in ('device', 'raw') and hasattr(dataset, 'collate')) else torch.utils.data.default_collate
+        collate = dataset.collate if (getattr(dataset, 'mode', None) in ('device', 'raw', 'packed') and hasattr(dataset, 'collate')) else torch.utils.data.default_collate
         self.page_wh = [(int(s['W_page']), int(s['H_page'])) for s, _ in items]
         pages = [s['background'] for s, _ in items]
         self.pages = self.pages_wh = None
         raw = [i for i, p in enumerate(pages) if isinstance(p, RawPage)]
-        if raw:                                                            # mode='raw': the same uint8 pages, decoded on the device
+        if raw:                                                            # mode='raw' / 'packed': the same uint8 pages, decoded on the device
             dec = decode_pages([pages[i] for i in raw], device)
             pages = list(pages)
             for j, i in enumerate(raw):

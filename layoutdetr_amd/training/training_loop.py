@@ -912,7 +912,7 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     training_set = construct_class_by_name(**training_set_kwargs)
     sampler = InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed)
     dl_kwargs = dict(data_loader_kwargs)
-    if getattr(training_set, 'mode', None) in ('device', 'raw') and hasattr(training_set, 'collate'):
+    if getattr(training_set, 'mode', None) in ('device', 'raw', 'packed') and hasattr(training_set, 'collate'):
         dl_kwargs.setdefault('collate_fn', training_set.collate)     # uint8 pages + 0-stride patch placeholder (dataset_layoutganpp.LayoutDataset)
     it = iter(torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus, **dl_kwargs))
     common = dict(num_bbox_labels=training_set.num_bbox_labels, img_channels=training_set.num_channels, img_height=training_set.height,
