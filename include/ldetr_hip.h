@@ -168,6 +168,16 @@ int ldetr_gemm_pair_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1, vo
 /* 1 if the pair would run as one launch, else 0. */
 int ldetr_gemm_pair_is_single_launch(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1);
 
+/* n <= LDETR_GEMM_GROUP_MAX independent small-tile problems (ta 0, tb 0: the nn.Linear form y = x W^T) as ONE grid of 32x32 tiles; every
+ * block finds its problem in the table (kernel arguments) and runs the device body ldetr_gemm_f32 runs for that problem alone, so each
+ * output is bit-equal to the single call.  The epilogue is alpha and col_bias only.  post_scale (NULL = all 1): one factor per problem,
+ * applied as a separate rounded fp32 multiply after the epilogue (bit-equal to a following element-wise `* post_scale`).  Returns the
+ * "unsupported" code (3), launching nothing, when a problem is not in the small-tile class, would split its reduction (K >= 1024 on few
+ * tiles), asks for another operand form or epilogue, or when the problems do not all resolve to the same instantiation (waves per block,
+ * scalar-addressed loads): the caller then issues them one by one. */
+#define LDETR_GEMM_GROUP_MAX 32
+int ldetr_gemm_small_group_f32(const ldetr_gemm_desc* g, const float* post_scale, int n, void* stream);
+
 int ldetr_conv2d_fwd_f32(const float* x, const ldetr_tensor4* xt, const float* w, int Cout, int KH, int KW, int stride,
                          int pad, float* y, int64_t ldy, int OH, int OW, const float* in_scale, int64_t in_scale_ld,
                          const ldetr_epilogue* ep, void* stream);
@@ -353,6 +363,10 @@ int ldetr_mul_reduce_f32(const float* a, const float* x, const float* scale, flo
  * x [B][P][C] NHWC pixels, C = 4 x a power of two <= 512. */
 int ldetr_torgb_fwd_f32(const float* x, const float* w, const float* styles, const float* bias, float* y,
                         int B, int64_t P, int C, void* stream);
+/* The same with the skip connection folded in: y = addend + (conv + bias), one more rounded add per value (bit-equal to an element-wise
+ * `addend + y` after ldetr_torgb_fwd_f32).  addend [B][P][3], required; it may be y itself. */
+int ldetr_torgb_fwd_add_f32(const float* x, const float* w, const float* styles, const float* bias, const float* addend, float* y,
+                            int B, int64_t P, int C, void* stream);
 int ldetr_torgb_bwd_f32(const float* x, const float* dy, const float* w, const float* styles, float* dx, float* dws,
                         float* dbias, int B, int64_t P, int C, void* stream);
 /* StyleGAN2 synthesis backward, everything between two contraction launches as one streaming pass over [B][P][C] (C a multiple of 4).  x is the
@@ -439,6 +453,37 @@ int ldetr_demod_fwd_f32(const float* weight, int64_t so, int64_t si, int64_t sh,
 int ldetr_demod_bwd_f32(const float* weight, int64_t so, int64_t si, int64_t sh, int64_t sw, const float* styles, const float* dcoefs,
                         const float* w2, const float* grad_dcoefs, float* dweight, int accumulate_dweight, float* dstyles, int B, int O,
                         int I, int KH, int KW, void* stream);
+
+/* The same for n <= LDETR_DEMOD_GROUP_MAX layers of one batch as ONE launch each way (the descriptors travel as kernel arguments).
+ * fwd: block = (layer, o) runs ldetr_demod_fwd_f32's body: bit-equal to n single calls.  bwd: the weight-gradient blocks (skipped for a layer
+ * whose dweight is NULL) and the style-gradient blocks of every layer in one grid; accumulate_dweight as above; add_dstyles != 0: dstyles +=
+ * (one rounded add onto what the buffer holds: the style gradient of the convolution path), else dstyles =.  grad_dcoefs and dstyles are
+ * required in bwd and unused in fwd.  B <= 64. */
+#define LDETR_DEMOD_GROUP_MAX 24
+typedef struct ldetr_demod_desc {
+    const float* weight; int64_t so, si, sh, sw;
+    const float* styles; float* dcoefs; float* w2;
+    const float* grad_dcoefs; float* dweight; float* dstyles;
+    int O, I, KH, KW;
+} ldetr_demod_desc;
+int ldetr_demod_group_fwd_f32(const ldetr_demod_desc* layers, int n, int B, float eps, void* stream);
+int ldetr_demod_group_bwd_f32(const ldetr_demod_desc* layers, int n, int B, int accumulate_dweight, int add_dstyles, void* stream);
+
+/* Backward of n <= LDETR_AFFINE_GROUP_MAX style affines  s_l = post_l * (gain_l * w A_l^T + bias_l)  that share one latent w [B][D]
+ * (SynthesisNetwork with one latent for every layer).  With scale_l = post_l * gain_l and ds_l [B][C_l] the gradient of s_l:
+ *   dlatent[b][k]  = sum_l scale_l * sum_c ds_l[b][c] * A_l[c][k]     ONE product over the concatenated channels, layers in table order, channels
+ *                    ascending; 64-channel partial sums meet in a second launch in that order (one writer per element: deterministic)
+ *   dA_l[c][k]    += scale_l * sum_b ds_l[b][c] * w[b][k]             (A_l, dA_l: [C_l][D] packed; dA may be NULL)
+ *   db_l[c]       += post_l * sum_b ds_l[b][c]                        (may be NULL)
+ * dlatent is written (=), or added to when accumulate_dlatent != 0.  scratch: scratch_floats >= B * D * sum_l ceil(C_l / 64) floats of
+ * device memory, no initialisation needed.  B <= 64.  Two launches. */
+#define LDETR_AFFINE_GROUP_MAX 32
+typedef struct ldetr_affine_desc {
+    const float* ds; const float* A; float* dA; float* db;
+    int C; float scale; float post;
+} ldetr_affine_desc;
+int ldetr_sg2_affine_bwd_f32(const ldetr_affine_desc* layers, int n, const float* latent, float* dlatent, int accumulate_dlatent,
+                             float* scratch, int64_t scratch_floats, int B, int D, void* stream);
 
 /* The generator phase's four layout losses on one set of generated boxes, fused with their gradients (training/loss.py:94,
  * metrics/metric_layoutnet.py:153-201,245-275): bbox, bbox_ref [B][N][4] (xc, yc, w, h), valid [B][N] (non-zero = real element),

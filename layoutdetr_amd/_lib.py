@@ -78,6 +78,18 @@ class WgradDesc(Structure):
                 ('M', c_int), ('rows', c_int), ('cols', c_int)]
 
 
+class DemodDesc(Structure):
+    """ldetr_demod_desc: one layer of a grouped demodulation launch."""
+    _fields_ = [('weight', c_void_p), ('so', c_int64), ('si', c_int64), ('sh', c_int64), ('sw', c_int64),
+                ('styles', c_void_p), ('dcoefs', c_void_p), ('w2', c_void_p), ('grad_dcoefs', c_void_p), ('dweight', c_void_p), ('dstyles', c_void_p),
+                ('O', c_int), ('I', c_int), ('KH', c_int), ('KW', c_int)]
+
+
+class AffineDesc(Structure):
+    """ldetr_affine_desc: one layer of the grouped style-affine backward."""
+    _fields_ = [('ds', c_void_p), ('A', c_void_p), ('dA', c_void_p), ('db', c_void_p), ('C', c_int), ('scale', c_float), ('post', c_float)]
+
+
 class LayoutRasterArgs(Structure):
     """ldetr_layout_raster_args."""
     _fields_ = [('struct_bytes', c_int), ('B', c_int), ('N', c_int), ('S', c_int), ('nrow', c_int), ('n_colors', c_int), ('n_pages', c_int),
@@ -193,6 +205,11 @@ SIGNATURES = {
     'ldetr_gemm_pair_is_single_launch': [_P, _P],
     'ldetr_demod_fwd_f32': [_P, _L, _L, _L, _L, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     'ldetr_demod_bwd_f32': [_P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    'ldetr_demod_group_fwd_f32': [_P, _I, _I, _F, _P],
+    'ldetr_demod_group_bwd_f32': [_P, _I, _I, _I, _I, _P],
+    'ldetr_sg2_affine_bwd_f32': [_P, _I, _P, _P, _I, _P, _L, _I, _I, _P],
+    'ldetr_gemm_small_group_f32': [_P, _P, _I, _P],
+    'ldetr_torgb_fwd_add_f32': [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P],
     'ldetr_layout_losses_f32': [_P, _P, _P, _I, _I, _P, _P, _P],
     'ldetr_layout_losses_bwd_f32': [_P, _P, _I, _I, _P, _P],
     'ldetr_layout_finish_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],

@@ -20,17 +20,16 @@ struct DemodParams {
     float* w2;                                 // [O][I]
     const float* g;                            // upstream gradient [B][O]
     float* dw; int dw_accumulate;              // same strides as w
-    float* ds;                                 // [B][I]
+    float* ds; int ds_add;                     // [B][I]; ds_add: += onto what the buffer holds (the style gradient of the conv path)
     int B, O, I, KH, KW;
     float eps;
 };
 
 constexpr int DEMOD_MAXB = 64;
 
-// grid O: W2 row of this output channel, then one dot product per sample
-__global__ __launch_bounds__(256) void demod_fwd_kernel(DemodParams p) {
+// block = output channel o: W2 row of this output channel, then one dot product per sample
+__device__ __forceinline__ void demod_fwd_body(const DemodParams& p, const int o) {
     extern __shared__ float w2row[];           // [I]
-    const int o = blockIdx.x;
     for (int i = threadIdx.x; i < p.I; i += 256) {
         const float* wp = p.w + (long)o * p.so + (long)i * p.si;
         float acc = 0.f;
@@ -67,10 +66,12 @@ __global__ __launch_bounds__(256) void demod_fwd_kernel(DemodParams p) {
     }
 }
 
-// grid O: weight gradient of this output channel
-__global__ __launch_bounds__(256) void demod_bwd_w_kernel(DemodParams p) {
+// grid O
+__global__ __launch_bounds__(256) void demod_fwd_kernel(DemodParams p) { demod_fwd_body(p, blockIdx.x); }
+
+// block = output channel o: weight gradient of this output channel
+__device__ __forceinline__ void demod_bwd_w_body(const DemodParams& p, const int o) {
     __shared__ float t[DEMOD_MAXB];
-    const int o = blockIdx.x;
     if (threadIdx.x < p.B) {
         const float dv = p.d[(long)threadIdx.x * p.O + o];
         t[threadIdx.x] = -0.5f * p.g[(long)threadIdx.x * p.O + o] * dv * dv * dv;
@@ -90,10 +91,13 @@ __global__ __launch_bounds__(256) void demod_bwd_w_kernel(DemodParams p) {
     }
 }
 
-// grid (ceil(I / 64), B): style gradient; block = 64 input channels x 4 lanes over the output channels
-__global__ __launch_bounds__(256) void demod_bwd_s_kernel(DemodParams p) {
+// grid O
+__global__ __launch_bounds__(256) void demod_bwd_w_kernel(DemodParams p) { demod_bwd_w_body(p, blockIdx.x); }
+
+// block (bx of ceil(I / 64), sample b): style gradient; 64 input channels x 4 lanes over the output channels
+__device__ __forceinline__ void demod_bwd_s_body(const DemodParams& p, const int bx, const int b) {
     extern __shared__ float tb[];              // [O] then [4][64] partial sums
-    const int b = blockIdx.y, i = blockIdx.x * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
+    const int i = bx * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
     for (int o = threadIdx.x; o < p.O; o += 256) {
         const float dv = p.d[(long)b * p.O + o];
         tb[o] = -0.5f * p.g[(long)b * p.O + o] * dv * dv * dv;
@@ -109,7 +113,40 @@ __global__ __launch_bounds__(256) void demod_bwd_s_kernel(DemodParams p) {
     __syncthreads();
     if (lane == 0 && i < p.I) {
         acc += part[threadIdx.x + 64] + part[threadIdx.x + 128] + part[threadIdx.x + 192];
-        p.ds[(long)b * p.I + i] = 2.f * p.s[(long)b * p.I + i] * acc;
+        const float v = 2.f * p.s[(long)b * p.I + i] * acc;
+        if (p.ds_add) p.ds[(long)b * p.I + i] = __fadd_rn(p.ds[(long)b * p.I + i], v); else p.ds[(long)b * p.I + i] = v;
+    }
+}
+
+// grid (ceil(I / 64), B)
+__global__ __launch_bounds__(256) void demod_bwd_s_kernel(DemodParams p) { demod_bwd_s_body(p, blockIdx.x, blockIdx.y); }
+
+// The same bodies for up to DEMOD_GROUP_MAX layers as ONE grid (the descriptors travel as kernel arguments, like wgrad_multi_kernel's): the
+// 13 demodulated layers of the 256^2 synthesis network are 13 launches of 10-19 us on [B, <= 512] tensors that do not depend on each other.
+// Forward: block = (layer, o).  Backward: the weight-gradient blocks (layer, o) first, then the style-gradient blocks (layer, bx, b).
+struct DemodGroup { DemodParams p[LDETR_DEMOD_GROUP_MAX]; int start_w[LDETR_DEMOD_GROUP_MAX + 1]; int start_s[LDETR_DEMOD_GROUP_MAX + 1]; int n; };
+
+__device__ __forceinline__ int group_find(const int* start, const int n, const int b) {
+    int pi = 0;
+    for (int i = 1; i < n; i++) pi += (b >= start[i]) ? 1 : 0;
+    return pi;
+}
+
+__global__ __launch_bounds__(256) void demod_group_fwd_kernel(DemodGroup g) {
+    const int pi = group_find(g.start_w, g.n, (int)blockIdx.x);
+    demod_fwd_body(g.p[pi], (int)blockIdx.x - g.start_w[pi]);
+}
+
+__global__ __launch_bounds__(256) void demod_group_bwd_kernel(DemodGroup g) {
+    const int blk = (int)blockIdx.x, nw = g.start_w[g.n];
+    if (blk < nw) {
+        const int pi = group_find(g.start_w, g.n, blk);
+        if (g.p[pi].dw) demod_bwd_w_body(g.p[pi], blk - g.start_w[pi]);
+    } else {
+        const int pi = group_find(g.start_s, g.n, blk - nw);
+        const DemodParams& p = g.p[pi];
+        const int r = blk - nw - g.start_s[pi], gx = (p.I + 63) >> 6;
+        demod_bwd_s_body(p, r % gx, r / gx);
     }
 }
 
@@ -153,4 +190,45 @@ extern "C" int ldetr_demod_bwd_f32(const float* weight, int64_t so, int64_t si, 
         rc = check_launch("demod_bwd_s");
     }
     return rc;
+}
+
+// Grouped forms: n layers of one batch as ONE launch each way.
+static int demod_group_fill(DemodGroup& g, const ldetr_demod_desc* d, int n, int B, float eps, bool bwd, int accumulate_dweight, int add_dstyles,
+                            size_t* lds, const char* what) {
+    LDETR_CHECK(d && n >= 1 && n <= LDETR_DEMOD_GROUP_MAX, "%s: 1..%d layers", what, LDETR_DEMOD_GROUP_MAX);
+    memset(&g, 0, sizeof(g));
+    g.n = n;
+    long tw = 0, ts = 0;
+    size_t need = 0;
+    for (int l = 0; l < n; l++) {
+        DemodParams& p = g.p[l];
+        const ldetr_demod_desc& q = d[l];
+        p.w = q.weight; p.so = q.so; p.si = q.si; p.sh = q.sh; p.sw = q.sw; p.s = q.styles; p.d = q.dcoefs; p.w2 = q.w2;
+        p.g = q.grad_dcoefs; p.dw = q.dweight; p.dw_accumulate = accumulate_dweight; p.ds = q.dstyles; p.ds_add = add_dstyles;
+        p.B = B; p.O = q.O; p.I = q.I; p.KH = q.KH; p.KW = q.KW; p.eps = eps;
+        int rc = demod_check(p, what); if (rc) return rc;
+        if (bwd) LDETR_CHECK(p.g && p.ds, "%s: null pointer (layer %d)", what, l);
+        g.start_w[l] = (int)tw; g.start_s[l] = (int)ts;
+        tw += p.O; ts += (long)cdiv(p.I, 64) * B;
+        const size_t mine = bwd ? (size_t)(p.O + 256) * sizeof(float) : (size_t)p.I * sizeof(float);
+        if (mine > need) need = mine;
+    }
+    LDETR_CHECK(tw + ts < 0x7fffffffL, "%s: grid too large", what);
+    g.start_w[n] = (int)tw; g.start_s[n] = (int)ts;
+    *lds = need;
+    return LDETR_OK;
+}
+
+extern "C" int ldetr_demod_group_fwd_f32(const ldetr_demod_desc* layers, int n, int B, float eps, void* stream) {
+    DemodGroup g; size_t lds = 0;
+    int rc = demod_group_fill(g, layers, n, B, eps, false, 0, 0, &lds, "demod_group_fwd"); if (rc) return rc;
+    hipLaunchKernelGGL(demod_group_fwd_kernel, dim3((unsigned)g.start_w[n]), 256, lds, (hipStream_t)stream, g);
+    return check_launch("demod_group_fwd");
+}
+
+extern "C" int ldetr_demod_group_bwd_f32(const ldetr_demod_desc* layers, int n, int B, int accumulate_dweight, int add_dstyles, void* stream) {
+    DemodGroup g; size_t lds = 0;
+    int rc = demod_group_fill(g, layers, n, B, 0.f, true, accumulate_dweight, add_dstyles, &lds, "demod_group_bwd"); if (rc) return rc;
+    hipLaunchKernelGGL(demod_group_bwd_kernel, dim3((unsigned)(g.start_w[n] + g.start_s[n])), 256, lds, (hipStream_t)stream, g);
+    return check_launch("demod_group_bwd");
 }

@@ -1187,8 +1187,9 @@ __device__ __forceinline__ void small_load_fast(const __amdgpu_buffer_rsrc_t& rs
 }
 
 // Body of one 32x32 tile (bx, by) and K slice bz of `sk`; shared by the single-problem kernel and the paired launch below.
-template <int TA, int TB, int NW, bool FAST = false>
-__device__ __forceinline__ void gemm_small_body(const GemmParams& p, const int bx, const int by, const int bz, const int sk, const int gx) {
+// POST (the grouped launch): `post` multiplies the finished value as one more rounded fp32 product, what an element-wise `* post` after the GEMM does.
+template <int TA, int TB, int NW, bool FAST = false, bool POST = false>
+__device__ __forceinline__ void gemm_small_body(const GemmParams& p, const int bx, const int by, const int bz, const int sk, const int gx, const float post = 1.f) {
     using f32x16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
     __shared__ float red[NW][32][33];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1334,6 +1335,10 @@ __device__ __forceinline__ void gemm_small_body(const GemmParams& p, const int b
             if (n0 + c4 + e < p.N) v[e] = apply_epilogue(ep, v[e], m, n0 + c4 + e, samp, p.ldc, inv_keep, ep.col_scale ? ep.col_scale[n0 + c4 + e] : 1.f, ep.col_bias ? ep.col_bias[n0 + c4 + e] : 0.f,
                                                              ep.residual ? ep.residual[(long)m * ep.ldr + n0 + c4 + e] : 0.f,
                                                              ep.mask_mode ? ep.mask_src[(long)m * ep.ldm + n0 + c4 + e] : 0.f);
+        if constexpr (POST) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) v[e] = __fmul_rn(v[e], post);
+        }
         if (n0 + c4 + 3 < p.N && (p.ldc & 3) == 0 && ((((uintptr_t)p.C) & 15) == 0)) {
             float4 o = make_float4(v[0], v[1], v[2], v[3]);
             if (ep.accumulate) { float4 c = *reinterpret_cast<float4*>(dst); o.x += c.x; o.y += c.y; o.z += c.z; o.w += c.w; }
@@ -1359,6 +1364,34 @@ __global__ __launch_bounds__(NW * 64) void gemm_small_pair_kernel(GemmParams p0,
     const int b = blockIdx.x;
     if (b < nt0 * sk0) { const int t = b % nt0; gemm_small_body<TA0, TB0, NW, FAST>(p0, t % gx0, t / gx0, b / nt0, sk0, gx0); }
     else { const int c = b - nt0 * sk0, t = c % nt1; gemm_small_body<TA1, TB1, NW, FAST>(p1, t % gx1, t / gx1, c / nt1, sk1, gx1); }
+}
+
+// Up to LDETR_GEMM_GROUP_MAX independent NN problems in ONE launch (the 20 style affines of the StyleGAN2 synthesis network: [B, 512] x
+// [512, C]^T each, 8-10 us apiece and nothing between them).  The table travels as kernel arguments in a compact form; a block expands its
+// problem into the GemmParams the single launch would carry and runs the same body, so every output is bit-equal to the problem launched alone.
+struct SmallGroupProblem {
+    const float* A; const float* B; float* C; const float* col_bias;
+    int lda, ldb, ldc, avec, bvec, M, N, K;
+    float alpha, post;
+};
+// ep0: the epilogue every problem starts from (fill_epilogue's defaults), passed as an argument so that the compiler sees run-time values where the
+// single launch sees them: with constants it would contract `v * alpha * col_scale + col_bias` differently and round once less.
+struct SmallGroup { SmallGroupProblem q[LDETR_GEMM_GROUP_MAX]; int start[LDETR_GEMM_GROUP_MAX + 1]; int n; GemmEpilogue ep0; };
+
+template <int NW, bool FAST>
+__global__ __launch_bounds__(NW * 64) void gemm_small_group_kernel(SmallGroup g) {
+    const int blk = (int)blockIdx.x;
+    int pi = 0;
+    for (int i = 1; i < g.n; i++) pi += (blk >= g.start[i]) ? 1 : 0;
+    const SmallGroupProblem& q = g.q[pi];
+    GemmParams p = {};
+    p.A.KW = p.A.KH = p.A.stride = p.A.C = p.A.Cr = 1; p.B.KW = p.B.KH = p.B.stride = p.B.C = p.B.Cr = 1;   // (init_operand)
+    p.A.p = q.A; p.A.ld = q.lda; p.A.vec = q.avec; p.B.p = q.B; p.B.ld = q.ldb; p.B.vec = q.bvec;
+    p.M = q.M; p.N = q.N; p.K = q.K; p.C = q.C; p.ldc = q.ldc;
+    p.splitk = 1; p.pstep = 1; p.nsamp = 1;
+    p.ep = g.ep0; p.ep.alpha = q.alpha; p.ep.col_bias = q.col_bias;
+    const int t = blk - g.start[pi], gx = (q.N + 31) >> 5;
+    gemm_small_body<0, 0, NW, FAST, true>(p, t % gx, t / gx, 0, 1, gx, q.post);
 }
 
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
@@ -1950,6 +1983,64 @@ extern "C" int ldetr_gemm_pair_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_d
     int rc = gemm_dense(*g0, stream);
     if (rc) return rc;
     return gemm_dense(*g1, stream);
+}
+
+// The grouped launch of NN problems: every problem must take, on its own, the unsplit small-tile kernel with the same (waves, FAST) pair.
+static int launch_small_group(const ldetr_gemm_desc* d, const float* post_scale, int n, hipStream_t st) {
+    SmallGroup g; memset(&g, 0, sizeof(g));
+    g.n = n;
+    fill_epilogue(g.ep0, nullptr);
+    long total = 0;
+    bool fast = false, w8 = false;
+    for (int i = 0; i < n; i++) {
+        const ldetr_gemm_desc& q = d[i];
+        LDETR_CHECK(q.A && q.B && q.C, "gemm_small_group: null pointer (problem %d)", i);
+        LDETR_CHECK(q.M > 0 && q.N > 0 && q.K > 0, "gemm_small_group: empty problem %d", i);
+        const ldetr_epilogue* e = q.ep;
+        const bool plain_ep = !e || (!e->col_scale && !e->samp_scale && !e->residual && e->act == 0 && e->mask_mode == 0 && e->out_scale == 1.f &&
+                                     e->p_drop == 0.f && !e->accumulate && !e->a_rowsum);
+        if (q.ta || q.tb || q.splitk != 0 || !plain_ep || !small_class(q.M, q.N, q.K)) {
+            set_error("gemm_small_group: problem %d is not a plain NN small-tile problem", i);
+            return LDETR_ERR_UNSUPPORTED;
+        }
+        const long blocks = (long)cdiv(q.N, 32) * cdiv(q.M, 32);
+        if (blocks <= 128 && q.K >= 1024) {   // (plan_small_split would split it)
+            set_error("gemm_small_group: problem %d splits its reduction", i);
+            return LDETR_ERR_UNSUPPORTED;
+        }
+        ldetr_gemm_desc one = q; one.pix_per_sample = 0;
+        const GemmParams p = fill_dense(one);
+        const bool f = small_fast_ok(p, 0, 0), w = small_wants8(blocks, 1, p.K);
+        if (i == 0) { fast = f; w8 = w; }
+        else if (f != fast || w != w8) {
+            set_error("gemm_small_group: problem %d resolves to another instantiation than problem 0", i);
+            return LDETR_ERR_UNSUPPORTED;
+        }
+        SmallGroupProblem& o = g.q[i];
+        LDETR_CHECK(q.lda < 0x7fffffffL && q.ldb < 0x7fffffffL && q.ldc < 0x7fffffffL, "gemm_small_group: leading dimension above 2^31 (problem %d)", i);
+        o.A = q.A; o.B = q.B; o.C = q.C; o.col_bias = p.ep.col_bias;
+        o.lda = (int)q.lda; o.ldb = (int)q.ldb; o.ldc = (int)q.ldc; o.avec = p.A.vec; o.bvec = p.B.vec; o.M = q.M; o.N = q.N; o.K = q.K;
+        o.alpha = p.ep.alpha; o.post = post_scale ? post_scale[i] : 1.f;
+        g.start[i] = (int)total;
+        total += blocks;
+    }
+    g.start[n] = (int)total;
+    const dim3 grid((unsigned)total);
+    if (fast) {
+        if (w8) hipLaunchKernelGGL((gemm_small_group_kernel<8, true>), grid, 512, 0, st, g);
+        else hipLaunchKernelGGL((gemm_small_group_kernel<4, true>), grid, 256, 0, st, g);
+    } else {
+        if (w8) hipLaunchKernelGGL((gemm_small_group_kernel<8, false>), grid, 512, 0, st, g);
+        else hipLaunchKernelGGL((gemm_small_group_kernel<4, false>), grid, 256, 0, st, g);
+    }
+    t_launches_f32++;
+    note_engine_launch(7, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, 1, total, 0);
+    return check_launch("gemm_small_group");
+}
+
+extern "C" int ldetr_gemm_small_group_f32(const ldetr_gemm_desc* g, const float* post_scale, int n, void* stream) {
+    LDETR_CHECK(g && n >= 1 && n <= LDETR_GEMM_GROUP_MAX, "gemm_small_group: 1..%d problems", LDETR_GEMM_GROUP_MAX);
+    return launch_small_group(g, post_scale, n, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

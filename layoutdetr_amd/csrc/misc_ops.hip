@@ -630,7 +630,7 @@ namespace ldetr {
 // One read of x, 12 bytes written per pixel: HBM-bound.  LPP = min(C / 4, 64) lanes share a pixel (a float4 of channels each, C / 4 / LPP
 // trips), their three partial dot products meet through xor shuffles.  On the contraction engine this launch pads 3 output channels to a
 // 64-wide tile: 144 us at 16 x 256 x 256 x 32 for 134 MB.
-struct RgbFwdParams { const float* x; const float* w; const float* s; const float* bias; float* y; long P; int B, C; };
+struct RgbFwdParams { const float* x; const float* w; const float* s; const float* bias; float* y; long P; int B, C; const float* add; };   // add [B][P][3] or NULL: y = add + (conv + bias), the skip connection
 
 template <int LPP>
 __global__ __launch_bounds__(256) void torgb_fwd_kernel(RgbFwdParams p) {
@@ -671,21 +671,26 @@ __global__ __launch_bounds__(256) void torgb_fwd_kernel(RgbFwdParams p) {
         for (int o = LPP / 2; o > 0; o >>= 1) { d0 += __shfl_xor(d0, o, 64); d1 += __shfl_xor(d1, o, 64); d2 += __shfl_xor(d2, o, 64); }
         if (lane_in == 0) {
             float* yr = p.y + ((long)b * p.P + r) * 3;
-            yr[0] = d0 + b0; yr[1] = d1 + b1; yr[2] = d2 + b2;
+            float y0 = d0 + b0, y1 = d1 + b1, y2 = d2 + b2;
+            if (p.add) {   // one more rounded add per value: what `img + y` after this launch computes
+                const float* ar = p.add + ((long)b * p.P + r) * 3;
+                y0 = __fadd_rn(ar[0], y0); y1 = __fadd_rn(ar[1], y1); y2 = __fadd_rn(ar[2], y2);
+            }
+            yr[0] = y0; yr[1] = y1; yr[2] = y2;
         }
     }
 }
 }  // namespace ldetr
 
 // x [B][P][C] (NHWC pixels), w [3][C], styles [B][C], bias [3] or NULL -> y [B][P][3].  C a multiple of 4 up to 512, a power of two in quads.
-extern "C" int ldetr_torgb_fwd_f32(const float* x, const float* w, const float* styles, const float* bias, float* y,
-                                   int B, int64_t P, int C, void* stream) {
+static int torgb_fwd(const float* x, const float* w, const float* styles, const float* bias, const float* addend, float* y,
+                     int B, int64_t P, int C, void* stream) {
     LDETR_CHECK(x && w && styles && y, "torgb_fwd: null pointer");
     const int C4 = C / 4;
     LDETR_CHECK(C % 4 == 0 && C4 >= 1 && C <= 512 && (C4 & (C4 - 1)) == 0, "torgb_fwd: C must be 4 x a power of two, at most 512 (got %d)", C);
     LDETR_CHECK((((uintptr_t)x | (uintptr_t)w | (uintptr_t)styles) & 15) == 0, "torgb_fwd: buffers must be 16-byte aligned");
     if (B == 0 || P == 0) return LDETR_OK;
-    RgbFwdParams p; p.x = x; p.w = w; p.s = styles; p.bias = bias; p.y = y; p.P = P; p.B = B; p.C = C;
+    RgbFwdParams p; p.x = x; p.w = w; p.s = styles; p.bias = bias; p.y = y; p.P = P; p.B = B; p.C = C; p.add = addend;
     const int lpp = C4 < 64 ? C4 : 64;
     const long ppb = 256 / lpp;
     long gx = (P + ppb - 1) / ppb; if (gx > 4096) gx = 4096;
@@ -701,6 +706,18 @@ extern "C" int ldetr_torgb_fwd_f32(const float* x, const float* w, const float* 
         default: hipLaunchKernelGGL(torgb_fwd_kernel<64>, grid, 256, 0, st, p); break;
     }
     return check_launch("torgb_fwd");
+}
+
+extern "C" int ldetr_torgb_fwd_f32(const float* x, const float* w, const float* styles, const float* bias, float* y,
+                                   int B, int64_t P, int C, void* stream) {
+    return torgb_fwd(x, w, styles, bias, nullptr, y, B, P, C, stream);
+}
+
+// The same with the skip connection folded in: y = addend + (conv + bias), addend [B][P][3] (the upsampled image of the block below; may be y itself).
+extern "C" int ldetr_torgb_fwd_add_f32(const float* x, const float* w, const float* styles, const float* bias, const float* addend, float* y,
+                                       int B, int64_t P, int C, void* stream) {
+    LDETR_CHECK(addend, "torgb_fwd_add: null addend");
+    return torgb_fwd(x, w, styles, bias, addend, y, B, P, C, stream);
 }
 
 // dws [B][3][C] and dbias [3] must be zeroed by the caller.

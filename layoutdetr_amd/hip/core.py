@@ -86,7 +86,7 @@ def engine_call(tag, flops, thunk, operands=(), nbytes=None):
 
 
 _P3_KINDS = {1: 'p3_nt_kernel', 2: 'p3_c3_kernel', 3: 'p3_tn_kernel', 4: 'p3_bwd_pair_nt_kernel', 5: 'p3_bwd_pair_c3_kernel'}
-_ENGINE_KINDS = {1: 'gemm_f32_kernel', 2: 'gemm_small_kernel', 3: 'gemm_small_pair_kernel', 4: 'conv3x3_c32_kernel', 5: 'wgrad_c32_3x3_kernel', 6: 'stem_conv7x7_kernel'}
+_ENGINE_KINDS = {1: 'gemm_f32_kernel', 2: 'gemm_small_kernel', 3: 'gemm_small_pair_kernel', 4: 'conv3x3_c32_kernel', 5: 'wgrad_c32_3x3_kernel', 6: 'stem_conv7x7_kernel', 7: 'gemm_small_group_kernel'}
 
 
 def launched_kernel(tag):
@@ -107,7 +107,7 @@ def launched_kernel(tag):
     name = _ENGINE_KINDS.get(kind, 'engine_?')
     if kind == 1:
         return f'{name}<{bm},{bn},{bk},{nw}w' + (',FAST' if fast else '') + (',SPLIT' if split else '') + '>' + (f' splitK={sk}' if sk > 1 else '')
-    if kind in (2, 3):
+    if kind in (2, 3, 7):
         return f'{name}<{nw}w' + (',FAST' if fast else '') + '>'
     if kind == 4:
         return 'conv3x3_c32_split_kernel' if split else name
@@ -300,6 +300,39 @@ def gemm_pair(g0, g1):
     descs, flops = _pair_descs(g0, g1)
     engine_call('gemm', flops, lambda: check(lib().ldetr_gemm_pair_f32(ctypes.byref(descs[0]), ctypes.byref(descs[1]), stream()), 'gemm_pair'),
                 nbytes=4.0 * sum(d.M * d.K + d.N * d.K + d.M * d.N for d in descs))
+
+
+GEMM_GROUP_MAX = 32      # LDETR_GEMM_GROUP_MAX
+
+
+def gemm_group(problems, post=None):
+    """Independent NN problems out = (alpha * A @ B^T + col_bias) * post as ONE launch (ldetr_gemm_small_group_f32): problems = dicts
+    (A, B, M, N, K, out, ep); post = one float per problem or None.  Every output is bit-equal to gemm(A, B, 0, 0, M, N, K, out, ep)
+    followed by `* post`.  -> False, with nothing launched, when the library cannot group them (a problem outside the small-tile class,
+    another epilogue, problems that resolve to different instantiations): the caller issues them one by one."""
+    n = len(problems)
+    if n < 1 or n > GEMM_GROUP_MAX:
+        return False
+    descs = (_lib.GemmDesc * n)()
+    flops = nbytes = 0.0
+    for d, g in zip(descs, problems):
+        require_gpu(g['A'], g['B'], g['out'])
+        d.A = g['A'].data_ptr(); d.lda = g['A'].stride(0); d.ta = 0
+        d.B = g['B'].data_ptr(); d.ldb = g['B'].stride(0); d.tb = 0
+        d.C = g['out'].data_ptr(); d.ldc = g['out'].stride(0)
+        d.M, d.N, d.K, d.splitk = int(g['M']), int(g['N']), int(g['K']), 0
+        d.ep = ctypes.addressof(g['ep']) if g.get('ep') is not None else None
+        d.pix_per_sample = 0
+        flops += 2.0 * d.M * d.N * d.K
+        nbytes += 4.0 * (d.M * d.K + d.N * d.K + d.M * d.N)
+    scales = (ctypes.c_float * n)(*[float(v) for v in post]) if post is not None else None
+    rc = engine_call('gemm', flops, lambda: lib().ldetr_gemm_small_group_f32(descs, scales, n, stream()), nbytes=nbytes)
+    if rc == 3:              # LDETR_ERR_UNSUPPORTED: not a group the library runs as one launch
+        if PROF.enabled and PROF.records:
+            PROF.records.pop()
+        return False
+    check(rc, 'gemm_small_group')
+    return True
 
 
 def colsum(a2d, B=1):

@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from ..hip import core, modconv, sg2_chain
+from ..hip import composite, core, modconv, sg2_chain
 from ..hip.linear import linear
 from ..torch_utils.ops import bias_act, upfirdn2d
 
@@ -206,24 +206,45 @@ class SynthesisNetwork(torch.nn.Module):
 
 
     def _forward_node(self, ws):
-        """The whole network as one autograd node (hip/sg2_chain.py): the affines and the demodulation coefficients per layer here, under
-        ordinary autograd, in the order the blocks' forwards compute them; the convolutions and everything between them inside the node."""
+        """The whole network as one autograd node (hip/sg2_chain.py).  With one latent for every layer the node owns the side chain as well: it is
+        handed the latent and, per layer, the affine's weight and bias next to the layer's own parameters, and issues the styles and the
+        demodulation coefficients as grouped launches.  Otherwise (per-layer latents, more than 64 samples, the twice-differentiable regulariser
+        phases, LDETR_DEBUG="SG2_SIDE=0") the affines and the coefficients run here, per layer, under ordinary autograd, in the order the blocks'
+        forwards compute them; the convolutions and everything between them inside the node either way."""
         blocks, tensors = [], []
         first = 0
+        side = sg2_chain.SIDE and ws.ndim == 2 and ws.is_cuda and ws.shape[0] <= sg2_chain.SIDE_MAX_B and not composite.active()
+        for res in self.block_resolutions:
+            block = getattr(self, f'b{res}')
+            for layer in ([block.conv0] if block.in_channels != 0 else []) + [block.conv1, block.torgb]:
+                a = layer.affine
+                side = side and a.activation == 'linear' and a.bias is not None and a.bias_gain == 1 and a.weight.shape[0] % 4 == 0
+        if side:
+            tensors.append(ws)
         for res in self.block_resolutions:
             block = getattr(self, f'b{res}')
             n = block.num_conv + block.num_torgb          # the block's toRGB shares its latent with the next block's first conv
             w_iter = iter([ws] * n if ws.ndim == 2 else ws[:, first:first + n].unbind(dim=1))
             layers = ([block.conv0] if block.in_channels != 0 else []) + [block.conv1]
-            for layer in layers:
+            names = (['conv0'] if block.in_channels != 0 else []) + ['conv1']
+            affines = {} if side else None
+            for name, layer in zip(names, layers):
+                if side:
+                    tensors += [layer.weight, layer.bias, layer.affine.weight, layer.affine.bias]
+                    affines[name] = (layer.affine.weight, layer.affine.bias, float(layer.affine.weight_gain), 1.0)
+                    continue
                 styles = layer.affine(next(w_iter))
                 tensors += [layer.weight, layer.bias, styles, modconv.demod_coefs(layer.weight, styles)]
-            tensors += [block.torgb.weight, block.torgb.bias, block.torgb.affine(next(w_iter)) * float(block.torgb.weight_gain)]
+            if side:
+                tensors += [block.torgb.weight, block.torgb.bias, block.torgb.affine.weight, block.torgb.affine.bias]
+                affines['torgb'] = (block.torgb.affine.weight, block.torgb.affine.bias, float(block.torgb.affine.weight_gain), float(block.torgb.weight_gain))
+            else:
+                tensors += [block.torgb.weight, block.torgb.bias, block.torgb.affine(next(w_iter)) * float(block.torgb.weight_gain)]
             gains = (float(block.conv0.act_gain) if block.in_channels != 0 else None, float(block.conv1.act_gain))
             params = {'conv1': (block.conv1.weight, block.conv1.bias), 'torgb': (block.torgb.weight, block.torgb.bias)}
             if block.in_channels != 0:
                 params['conv0'] = (block.conv0.weight, block.conv0.bias)
-            blocks.append(sg2_chain.Block(block.in_channels != 0, gains, params))
+            blocks.append(sg2_chain.Block(block.in_channels != 0, gains, params, affines))
             first += block.num_conv
         b4 = getattr(self, f'b{self.block_resolutions[0]}')
         img = sg2_chain.run(blocks, b4.const, b4.resample_filter, tensors)
