@@ -168,6 +168,12 @@ int ldetr_gemm_pair_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1, vo
 /* 1 if the pair would run as one launch, else 0. */
 int ldetr_gemm_pair_is_single_launch(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1);
 
+/* Two INDEPENDENT problems of the nn.Linear form (ta 0, tb 0), each with its own full epilogue (bias, activation, dropout, residual) and its own
+ * M, as ONE launch of the small-tile pair kernel: each half is planned as ldetr_gemm_f32 plans it alone (waves, split-K, workspace slice) and
+ * runs the same device body, so its output is bit-equal to the single call.  Returns the "unsupported" code (3), launching nothing, when a half
+ * is outside the small-tile class or the halves resolve to different instantiations (waves per block, scalar-addressed loads). */
+int ldetr_gemm_pair_fwd_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1, void* stream);
+
 /* n <= LDETR_GEMM_GROUP_MAX independent small-tile problems (ta 0, tb 0: the nn.Linear form y = x W^T) as ONE grid of 32x32 tiles; every
  * block finds its problem in the table (kernel arguments) and runs the device body ldetr_gemm_f32 runs for that problem alone, so each
  * output is bit-equal to the single call.  The epilogue is alpha and col_bias only.  post_scale (NULL = all 1): one factor per problem,
@@ -214,6 +220,22 @@ int ldetr_attention_bwd_f32(const float* q, int64_t ldq, const float* k, int64_t
                             const float* dout, int64_t lddo, float* dq, int64_t lddq, float* dk, int64_t lddk,
                             float* dv, int64_t lddv, int B, int H, int Lq, int Lk, int head_dim, float scale,
                             float p_drop, uint64_t seed, const uint64_t* seed_ptr, int causal, void* stream);
+
+/* One or two independent attention forward problems (the arguments of ldetr_attention_fwd_f32, one block per problem) as ONE launch: problem 1's
+ * blocks follow problem 0's in the grid and run the same device code, so each output is bit-equal to the single call on that problem; dropout
+ * seed and offset are per problem.  n == 1 is the single call.  Returns the "unsupported" code (3), launching nothing, when head_dim != 32 or
+ * the two problems would not run the same kernel instantiation alone (Lq below / above 48, another number of key tiles, more than 256 keys):
+ * the caller then issues them one by one. */
+typedef struct ldetr_attn_args {
+    const float* q; int64_t ldq; const float* k; int64_t ldk; const float* v; int64_t ldv;
+    const unsigned char* key_padding_mask;
+    float* out; int64_t ldo; float* lse;
+    int B, H, Lq, Lk, head_dim;
+    float scale, p_drop;
+    uint64_t seed; const uint64_t* seed_ptr;
+    int causal;
+} ldetr_attn_args;
+int ldetr_attention_fwd_group_f32(const ldetr_attn_args* a, int n, void* stream);
 
 /* Second stage of ldetr_torgb_bwd_f32 (ToRGBLayer backward, training/networks_stylegan2.py:349-353): dws [B][3][C] ->
  * dw[o][c] += sum_b dws[b][o][c] s[b][c] (accumulated) and ds[b][c] = sum_o dws[b][o][c] w[o][c]. */

@@ -49,6 +49,13 @@ class LnArgs(Structure):
                 ('dy_parts', c_void_p), ('dy_nparts', c_int), ('dy_part_stride', c_int64)]
 
 
+class AttnArgs(Structure):
+    """ldetr_attn_args: one attention forward problem of ldetr_attention_fwd_group_f32."""
+    _fields_ = [('q', c_void_p), ('ldq', c_int64), ('k', c_void_p), ('ldk', c_int64), ('v', c_void_p), ('ldv', c_int64), ('key_padding_mask', c_void_p),
+                ('out', c_void_p), ('ldo', c_int64), ('lse', c_void_p), ('B', c_int), ('H', c_int), ('Lq', c_int), ('Lk', c_int), ('head_dim', c_int),
+                ('scale', c_float), ('p_drop', c_float), ('seed', c_uint64), ('seed_ptr', c_void_p), ('causal', c_int)]
+
+
 class FfnArgs(Structure):
     """ldetr_ffn_args."""
     _fields_ = [('x', c_void_p), ('ldx', c_int64), ('w1', c_void_p), ('b1', c_void_p), ('w2', c_void_p), ('h', c_void_p), ('ypart', c_void_p),
@@ -203,6 +210,8 @@ SIGNATURES = {
     'ldetr_sg2_handoff_f32': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _P],
     'ldetr_gemm_pair_f32': [_P, _P, _P],
     'ldetr_gemm_pair_is_single_launch': [_P, _P],
+    'ldetr_gemm_pair_fwd_f32': [_P, _P, _P],
+    'ldetr_attention_fwd_group_f32': [_P, _I, _P],
     'ldetr_demod_fwd_f32': [_P, _L, _L, _L, _L, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     'ldetr_demod_bwd_f32': [_P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'ldetr_demod_group_fwd_f32': [_P, _I, _I, _F, _P],

@@ -48,12 +48,13 @@ __device__ __forceinline__ float attn_drop(const AttnParams& p, int bh, int q, i
 }
 
 // DHC = head_dim / 32 (1 for the DETR blocks; 2..6 for the BERT text encoder's 64..192-wide heads, forward only).
+// (the body takes the block index as an argument: the two-problem launch below numbers the second problem's blocks after the first's)
 template <int NKT, int DHC>
-__global__ __launch_bounds__(64) void attn_fwd_kernel(AttnParams p) {
+__device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int blk) {
     constexpr int DH = 32 * DHC;
     const int nqt = (p.Lq + 15) >> 4;
-    const int qt = blockIdx.x % nqt;
-    const int bh = blockIdx.x / nqt;
+    const int qt = blk % nqt;
+    const int bh = blk / nqt;
     const int b = bh / p.H, h = bh - b * p.H;
     const int lane = threadIdx.x, li = lane & 15, g = lane >> 4;
     const int q0 = qt << 4;
@@ -121,6 +122,20 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnParams p) {
 #pragma unroll
         for (int c = 0; c < 2 * DHC; c++) *reinterpret_cast<float4*>(op + 16 * c) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
     }
+}
+
+template <int NKT, int DHC>
+__global__ __launch_bounds__(64) void attn_fwd_kernel(AttnParams p) {
+    attn_fwd_body<NKT, DHC>(p, (int)blockIdx.x);
+}
+
+// Two independent attention problems of one instantiation in ONE grid: blocks [0, nb0) are problem pa's, the rest pb's (the (pa, pb, nb0) form of
+// mha_small.hip).  Each block runs the single launch's body on its own problem, so both outputs are bit-equal to the single launches.
+template <int NKT, int DHC>
+__global__ __launch_bounds__(64) void attn_fwd_pair_kernel(AttnParams pa, AttnParams pb, int nb0) {
+    const int blk = (int)blockIdx.x;
+    if (blk < nb0) attn_fwd_body<NKT, DHC>(pa, blk);
+    else attn_fwd_body<NKT, DHC>(pb, blk - nb0);
 }
 
 // Long-key forward (Lk > 256: background_size above 512, i.e. more than 16x16 trunk positions).  Same wave layout as
@@ -219,12 +234,12 @@ __global__ __launch_bounds__(64) void attn_fwd_long_kernel(AttnParams p) {
 // Row pitch DH + 4 floats: the MFMA operand reads Ks[key li][4 kk + g] and Vs[key 4 g + t][16 c + li] then touch every bank
 // exactly twice per 64 lanes, the minimum.  NCH = number of 64-key chunks (Lk <= 64 NCH).
 template <int NCH, int DHC>
-__global__ __launch_bounds__(256) void attn_fwd_wide_kernel(AttnParams p) {
+__device__ __forceinline__ void attn_fwd_wide_body(const AttnParams& p, const int blk) {
     constexpr int DH = 32 * DHC, DHP = DH + 4, NKT = 4 * NCH;
     extern __shared__ __attribute__((aligned(16))) float kv_tile[];      // [64][DHP]
     const int nq64 = (p.Lq + 63) >> 6;
-    const int qb = blockIdx.x % nq64;
-    const int bh = blockIdx.x / nq64;
+    const int qb = blk % nq64;
+    const int bh = blk / nq64;
     const int b = bh / p.H, h = bh - b * p.H;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
     const int qrow = (qb << 6) + (wave << 4) + li;
@@ -312,6 +327,19 @@ __global__ __launch_bounds__(256) void attn_fwd_wide_kernel(AttnParams p) {
 #pragma unroll
         for (int cc = 0; cc < 2 * DHC; cc++) *reinterpret_cast<float4*>(op + 16 * cc) = make_float4(o[cc][0], o[cc][1], o[cc][2], o[cc][3]);
     }
+}
+
+template <int NCH, int DHC>
+__global__ __launch_bounds__(256) void attn_fwd_wide_kernel(AttnParams p) {
+    attn_fwd_wide_body<NCH, DHC>(p, (int)blockIdx.x);
+}
+
+// The two-problem form of the wide kernel (attn_fwd_pair_kernel's block numbering; the branch is block-uniform, so the barriers inside the body are safe).
+template <int NCH, int DHC>
+__global__ __launch_bounds__(256) void attn_fwd_wide_pair_kernel(AttnParams pa, AttnParams pb, int nb0) {
+    const int blk = (int)blockIdx.x;
+    if (blk < nb0) attn_fwd_wide_body<NCH, DHC>(pa, blk);
+    else attn_fwd_wide_body<NCH, DHC>(pb, blk - nb0);
 }
 
 // Backward, query-major half: dQ for one 16-query tile.
@@ -625,6 +653,22 @@ static int check_attn(const AttnParams& p, const char* what) {
 
 using namespace ldetr;
 
+// The one routing rule of the forward entries (single and group): 0 = attn_fwd_long_kernel (more than 256 keys: chunked online softmax),
+// 1 = attn_fwd_kernel<*tmpl key tiles, .>, 2 = attn_fwd_wide_kernel<*tmpl 64-key chunks, .>: wide heads (the BERT text models), and 32-wide heads
+// too when a block's four query tiles are mostly real (the DETR encoder's 64 x 64 self-attention), with K / V rows that take 16-byte loads.
+static int attn_fwd_route(const AttnParams& p, int head_dim, int* tmpl) {
+    const int nkt = (p.Lk + 15) / 16;
+    *tmpl = 0;
+    if (nkt > 16) return 0;
+    if ((head_dim >= 64 || p.Lq >= 48) && (p.ldk % 4) == 0 && (p.ldv % 4) == 0 && ((((uintptr_t)p.k) | ((uintptr_t)p.v)) & 15) == 0) {
+        const int nch = (p.Lk + 63) / 64;
+        *tmpl = nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 3 ? 3 : 4;
+        return 2;
+    }
+    *tmpl = nkt <= 1 ? 1 : nkt <= 2 ? 2 : nkt <= 4 ? 4 : nkt <= 8 ? 8 : 16;
+    return 1;
+}
+
 extern "C" int ldetr_attention_fwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                                        const unsigned char* key_padding_mask, float* out, int64_t ldo, float* lse,
                                        int B, int H, int Lq, int Lk, int head_dim, float scale,
@@ -637,18 +681,20 @@ extern "C" int ldetr_attention_fwd_f32(const float* q, int64_t ldq, const float*
     LDETR_CHECK(!causal || Lq == Lk, "attention_fwd: the causal mask is defined for self-attention (Lq == Lk)");
     int rc = check_attn(p, "attention_fwd");
     if (rc) return rc;
-    const int nqt = (Lq + 15) / 16, nkt = (Lk + 15) / 16;
+    const int nqt = (Lq + 15) / 16;
     const int grid = B * H * nqt;
     hipStream_t st = (hipStream_t)stream;
+    int tmpl = 0;
+    const int route = attn_fwd_route(p, head_dim, &tmpl);
 #define LDETR_ATTN_FWD(DHC)                                                                     \
     do {                                                                                         \
-        if (nkt <= 1) hipLaunchKernelGGL((attn_fwd_kernel<1, DHC>), grid, 64, 0, st, p);         \
-        else if (nkt <= 2) hipLaunchKernelGGL((attn_fwd_kernel<2, DHC>), grid, 64, 0, st, p);    \
-        else if (nkt <= 4) hipLaunchKernelGGL((attn_fwd_kernel<4, DHC>), grid, 64, 0, st, p);    \
-        else if (nkt <= 8) hipLaunchKernelGGL((attn_fwd_kernel<8, DHC>), grid, 64, 0, st, p);    \
+        if (tmpl == 1) hipLaunchKernelGGL((attn_fwd_kernel<1, DHC>), grid, 64, 0, st, p);        \
+        else if (tmpl == 2) hipLaunchKernelGGL((attn_fwd_kernel<2, DHC>), grid, 64, 0, st, p);   \
+        else if (tmpl == 4) hipLaunchKernelGGL((attn_fwd_kernel<4, DHC>), grid, 64, 0, st, p);   \
+        else if (tmpl == 8) hipLaunchKernelGGL((attn_fwd_kernel<8, DHC>), grid, 64, 0, st, p);   \
         else hipLaunchKernelGGL((attn_fwd_kernel<16, DHC>), grid, 64, 0, st, p);                 \
     } while (0)
-    if (nkt > 16) {     // long key sequences: chunked online softmax
+    if (route == 0) {     // long key sequences: chunked online softmax
         switch (head_dim / 32) {
             case 1: hipLaunchKernelGGL((attn_fwd_long_kernel<1>), grid, 64, 0, st, p); break;
             case 2: hipLaunchKernelGGL((attn_fwd_long_kernel<2>), grid, 64, 0, st, p); break;
@@ -659,10 +705,9 @@ extern "C" int ldetr_attention_fwd_f32(const float* q, int64_t ldq, const float*
         }
         return check_launch("attention_fwd_long");
     }
-    // wide heads (the BERT text models): LDS-staged K / V shared by four query tiles per block
-    // (32-wide heads too when a block's four query tiles are mostly real: the DETR encoder's 64 x 64 self-attention; bit 1 of the switch)
-    if ((head_dim >= 64 || Lq >= 48) && (ldk % 4) == 0 && (ldv % 4) == 0 && ((((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0) {
-        const int nch = (Lk + 63) / 64, wgrid = B * H * ((Lq + 63) / 64);
+    // wide kernel: LDS-staged K / V shared by four query tiles per block (attn_fwd_route)
+    if (route == 2) {
+        const int nch = tmpl, wgrid = B * H * ((Lq + 63) / 64);
 #define LDETR_ATTN_WIDE(NCH, DHC)                                                                                         \
     do {                                                                                                                   \
         constexpr size_t lds = (size_t)64 * (32 * DHC + 4) * sizeof(float);                                                \
@@ -695,6 +740,59 @@ extern "C" int ldetr_attention_fwd_f32(const float* q, int64_t ldq, const float*
     }
 #undef LDETR_ATTN_FWD
     return check_launch("attention_fwd");
+}
+
+// Two independent attention problems (32-wide heads) as ONE launch: problem 1's blocks follow problem 0's in the grid and every block runs the body
+// the single launch runs, so each output is bit-equal to ldetr_attention_fwd_f32 on that problem.  Dropout seed / offset are per problem.
+// n == 1: the single launch.  LDETR_ERR_UNSUPPORTED, with nothing launched, when the two problems resolve to different kernels (or to the long-key
+// one, or have wider heads): the caller issues them singly.
+extern "C" int ldetr_attention_fwd_group_f32(const ldetr_attn_args* a, int n, void* stream) {
+    LDETR_CHECK(a && (n == 1 || n == 2), "attention_fwd_group: 1 or 2 problems");
+    if (n == 1)
+        return ldetr_attention_fwd_f32(a->q, a->ldq, a->k, a->ldk, a->v, a->ldv, a->key_padding_mask, a->out, a->ldo, a->lse, a->B, a->H, a->Lq, a->Lk,
+                                       a->head_dim, a->scale, a->p_drop, a->seed, a->seed_ptr, a->causal, stream);
+    AttnParams p[2];
+    int route[2], tmpl[2] = {0, 0};
+    for (int i = 0; i < 2; i++) {
+        const ldetr_attn_args& s = a[i];
+        if (s.head_dim != 32) {
+            set_error("attention_fwd_group: 32-wide heads only (problem %d has %d)", i, s.head_dim);
+            return LDETR_ERR_UNSUPPORTED;
+        }
+        AttnParams& q = p[i]; memset(&q, 0, sizeof(q));
+        q.q = s.q; q.k = s.k; q.v = s.v; q.ldq = s.ldq; q.ldk = s.ldk; q.ldv = s.ldv; q.kpm = s.key_padding_mask;
+        q.o = s.out; q.ldo = s.ldo; q.lse = s.lse; q.B = s.B; q.H = s.H; q.Lq = s.Lq; q.Lk = s.Lk;
+        q.scale = s.scale; q.p_drop = s.p_drop; q.seed = s.seed; q.seed_ptr = (const unsigned long long*)s.seed_ptr; q.causal = s.causal;
+        LDETR_CHECK(!s.causal || s.Lq == s.Lk, "attention_fwd_group: the causal mask is defined for self-attention (Lq == Lk)");
+        int rc = check_attn(q, "attention_fwd_group");
+        if (rc) return rc;
+        route[i] = attn_fwd_route(q, s.head_dim, &tmpl[i]);
+    }
+    if (route[0] == 0 || route[0] != route[1] || tmpl[0] != tmpl[1]) {
+        set_error("attention_fwd_group: the problems resolve to different kernels");
+        return LDETR_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (route[0] == 2) {
+        const int nb0 = p[0].B * p[0].H * ((p[0].Lq + 63) / 64), nb1 = p[1].B * p[1].H * ((p[1].Lq + 63) / 64);
+        constexpr size_t lds = (size_t)64 * (32 + 4) * sizeof(float);
+        switch (tmpl[0]) {
+            case 1: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<1, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
+            case 2: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<2, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
+            case 3: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<3, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
+            default: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<4, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
+        }
+        return check_launch("attention_fwd_wide_pair");
+    }
+    const int nb0 = p[0].B * p[0].H * ((p[0].Lq + 15) / 16), nb1 = p[1].B * p[1].H * ((p[1].Lq + 15) / 16);
+    switch (tmpl[0]) {
+        case 1: hipLaunchKernelGGL((attn_fwd_pair_kernel<1, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
+        case 2: hipLaunchKernelGGL((attn_fwd_pair_kernel<2, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
+        case 4: hipLaunchKernelGGL((attn_fwd_pair_kernel<4, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
+        case 8: hipLaunchKernelGGL((attn_fwd_pair_kernel<8, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
+        default: hipLaunchKernelGGL((attn_fwd_pair_kernel<16, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
+    }
+    return check_launch("attention_fwd_pair");
 }
 
 extern "C" int ldetr_attention_bwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,

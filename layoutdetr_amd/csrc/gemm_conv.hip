@@ -1441,13 +1441,18 @@ float* scratch_alloc(size_t bytes) {
 
 // Split-K plan of a small-tile problem: few tiles + a long reduction (the decoders' 2048-wide FFN on 144 rows) would have 40 blocks
 // walk K one after the other; split K over up to 8 blocks per tile (>= 256 of K each) and reduce through the workspace in-kernel.
-static int plan_small_split(GemmParams& p, long blocks) {
+static int small_split_factor(int K, long blocks) {   // the rule alone: nothing is allocated
     int sk = 1;
-    if (blocks <= 128 && p.K >= 1024) {
-        sk = p.K / 256; if (sk > 8) sk = 8;
+    if (blocks <= 128 && K >= 1024) {
+        sk = K / 256; if (sk > 8) sk = 8;
         while (sk > 1 && blocks * sk > 640) sk--;
-        if (sk > 1 && !ring_alloc(blocks, (size_t)blocks * sk * 1024 * sizeof(float), &p.ws_count, &p.ws)) sk = 1;
     }
+    return sk;
+}
+
+static int plan_small_split(GemmParams& p, long blocks) {
+    int sk = small_split_factor(p.K, blocks);
+    if (sk > 1 && !ring_alloc(blocks, (size_t)blocks * sk * 1024 * sizeof(float), &p.ws_count, &p.ws)) sk = 1;
     return sk;
 }
 
@@ -1983,6 +1988,49 @@ extern "C" int ldetr_gemm_pair_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_d
     int rc = gemm_dense(*g0, stream);
     if (rc) return rc;
     return gemm_dense(*g1, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Two INDEPENDENT nn.Linear-shaped problems (ta 0, tb 0), each with its own full epilogue, as ONE launch of gemm_small_pair_kernel<0, 0, 0, 0>:
+// the same projection of two encoder stacks that advance in lock-step (training/detr_transformer.py, the rider).  Each half is planned exactly as
+// launch_small<0, 0> plans it alone (split-K and workspace slice from the rings, in call order) and runs the same device body, so its output is
+// bit-equal to the single call.  LDETR_ERR_UNSUPPORTED, with nothing launched, when a half is outside the small-tile class or the halves resolve to
+// different (waves, FAST) instantiations: the caller issues them singly.
+extern "C" int ldetr_gemm_pair_fwd_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_desc* g1, void* stream) {
+    LDETR_CHECK(g0 && g1, "gemm_pair_fwd: null descriptor");
+    const ldetr_gemm_desc* gs[2] = {g0, g1};
+    for (int i = 0; i < 2; i++) {
+        const ldetr_gemm_desc& q = *gs[i];
+        LDETR_CHECK(q.A && q.B && q.C, "gemm_pair_fwd: null pointer (problem %d)", i);
+        if (q.ta || q.tb || !small_class(q) || (q.ep && (q.ep->a_rowsum || q.ep->samp_scale))) {
+            set_error("gemm_pair_fwd: problem %d is not an NT small-tile problem", i);
+            return LDETR_ERR_UNSUPPORTED;
+        }
+    }
+    GemmParams p0 = fill_dense(*g0), p1 = fill_dense(*g1);
+    const int gx0 = cdiv(p0.N, 32), nt0 = gx0 * cdiv(p0.M, 32), gx1 = cdiv(p1.N, 32), nt1 = gx1 * cdiv(p1.M, 32);
+    const bool fast = small_fast_ok(p0, 0, 0);
+    if (fast != small_fast_ok(p1, 0, 0)) {
+        set_error("gemm_pair_fwd: the problems resolve to different instantiations (FAST)");
+        return LDETR_ERR_UNSUPPORTED;
+    }
+    // the wave counts are compared on the split factors of the rule alone first, so that a refused pair has taken no workspace slice
+    if (small_wants8(nt0, small_split_factor(p0.K, nt0), p0.K) != small_wants8(nt1, small_split_factor(p1.K, nt1), p1.K)) {
+        set_error("gemm_pair_fwd: the problems resolve to different instantiations (waves)");
+        return LDETR_ERR_UNSUPPORTED;
+    }
+    const int sk0 = plan_small_split(p0, nt0), sk1 = plan_small_split(p1, nt1);
+    const bool w8 = small_wants8(nt0, sk0, p0.K);
+    if (w8 != small_wants8(nt1, sk1, p1.K)) {
+        // (only when the workspace could not serve one of the two splits: the slice the other half took is left to the ring, which is harmless --
+        // the single launches that follow take fresh ones)
+        set_error("gemm_pair_fwd: the problems resolve to different instantiations (waves, one split without workspace)");
+        return LDETR_ERR_UNSUPPORTED;
+    }
+    const dim3 grid((unsigned)(nt0 * sk0 + nt1 * sk1));
+    launch_small_kernel<0, 0, 0, 0>(fast, w8, grid, (hipStream_t)stream, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
+    note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, sk0 * 256 + sk1, (long)grid.x, 0);
+    return check_launch("gemm_small_pair_fwd");
 }
 
 // The grouped launch of NN problems: every problem must take, on its own, the unsplit small-tile kernel with the same (waves, FAST) pair.

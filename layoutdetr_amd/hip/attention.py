@@ -10,7 +10,7 @@ import math
 
 import torch
 
-from . import core
+from . import core, rider
 from .linear import linear
 
 
@@ -73,10 +73,13 @@ class _AttnPackedFn(torch.autograd.Function):
         lse = torch.empty((B * H * L,), device=qkv.device, dtype=torch.float32)
         seed = core.next_seed() if p_drop > 0 else 0
         scale = 1.0 / math.sqrt(dh)
-        core.check(core.lib().ldetr_attention_fwd_f32(
-            core.ptr(q), q.stride(0), core.ptr(k), k.stride(0), core.ptr(v), v.stride(0), core.ptr(kpm),
-            core.ptr(out), d, core.ptr(lse), B, H, L, L, dh, scale, p_drop, seed, core.seed_ptr() if p_drop > 0 else None,
-            1 if causal else 0, core.stream()), 'attention_fwd')
+        if rider.MODE is not None:      # an encoder stack in lock-step with another one: queued, or sent with the other's launch
+            rider.attention(q, k, v, kpm, out, lse, B, H, L, dh, scale, p_drop, seed, 1 if causal else 0)
+        else:
+            core.check(core.lib().ldetr_attention_fwd_f32(
+                core.ptr(q), q.stride(0), core.ptr(k), k.stride(0), core.ptr(v), v.stride(0), core.ptr(kpm),
+                core.ptr(out), d, core.ptr(lse), B, H, L, L, dh, scale, p_drop, seed, core.seed_ptr() if p_drop > 0 else None,
+                1 if causal else 0, core.stream()), 'attention_fwd')
         ctx.save_for_backward(qkv, v_sep, kpm, out, lse)
         ctx.cfg = (B, H, L, dh, scale, p_drop, seed, 1 if causal else 0)
         return out

@@ -5,7 +5,7 @@ hip.layernorm / hip.ffn (one sub-block per autograd node) and hip.stacks (a whol
 import math
 
 from .. import _lib
-from . import core
+from . import core, rider
 
 D_MODEL, N_HEAD = 256, 8
 SCALE = 1.0 / math.sqrt(D_MODEL // N_HEAD)      # the attention sub-blocks are built for d_model 256 with 8 heads
@@ -22,6 +22,8 @@ def launch(what, args, flops=0.0, nbytes=0.0):
     """One launch of 1-2 problems (`args`: argument blocks of one builder); flops > 0: a contraction launch, accounted with the engine's
     (bench.py roofline leg, hip.core.engine_call)."""
     entry, grouped = _ENTRIES[what]
+    if rider.takes_block(what, args):      # an encoder stack in lock-step with another one: queued, or sent with the other's launch
+        return rider.block(what, args[0])
     fn = getattr(core.lib(), entry)
     n = len(args)
     arr = (type(args[0]) * n)(*args)
@@ -64,6 +66,9 @@ def ln_fwd(x, r, gamma, beta, eps, p_drop, seed, y, z, mean, rstd, r_parts=0, r_
     a.r_bias = _p(r_bias) if r_parts > 0 else None
     if pos is not None:
         a.pos, a.pos_rows, a.ypos = pos.data_ptr(), pos.shape[0], ypos.data_ptr()
+    if rider.MODE == 'record':
+        a._keep = (x, r, gamma, beta, y, z, mean, rstd, r_bias, pos, ypos)      # a queued launch keeps its tensors alive
+        a._outs = (y, z, mean, rstd, ypos)
     return a
 
 
@@ -88,6 +93,9 @@ def ffn_fwd(x, w1, b1, w2, h, ypart, p_drop, seed):
     a.x, a.ldx, a.w1, a.b1, a.w2, a.h, a.ypart = x.data_ptr(), x.stride(0), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), h.data_ptr(), ypart.data_ptr()
     a.M, a.F = h.shape
     _set_dropout(a, p_drop, seed)
+    if rider.MODE == 'record':
+        a._keep = (x, w1, b1, w2, h, ypart)
+        a._outs = (h, ypart)
     return a
 
 

@@ -122,6 +122,7 @@ def engine_launch_counts():
 
 
 
+_rider = None      # hip.rider once it is imported (it imports this module)
 _workspace = {}
 WORKSPACE_BYTES = int(os.environ.get('LDETR_WORKSPACE_MIB', '256')) << 20   # split-K scratch per device
 
@@ -167,6 +168,8 @@ def require_gpu(*tensors):
 
 
 def stream():
+    if _rider is not None and _rider.MODE == 'record':
+        raise RuntimeError('a launch that hip.rider does not queue was issued while an encoder stack was being recorded')
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -180,16 +183,62 @@ def f32c(t):
     """fp32 + contiguous (no copy when already so)."""
     if t is None:
         return None
+    if _rider is not None and _rider.MODE == 'record' and (t.dtype != torch.float32 or not t.is_contiguous()):
+        _rider.check_ready(t, 'f32c (copy)')
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
 
 
+def _seed_at(position):
+    base = int(torch.initial_seed()) & 0xFFFFFFFF
+    return ((base << 32) ^ (position * 0x9E3779B1)) & 0xFFFFFFFFFFFFFFFF
+
+
 def next_seed():
     """Per-launch dropout seed derived from torch's CPU generator (so torch.manual_seed controls it)."""
+    if _seed_lease[0] is not None:
+        return _seed_lease[0].draw()
     _seed_counter[0] += 1
-    base = int(torch.initial_seed()) & 0xFFFFFFFF
-    return ((base << 32) ^ (_seed_counter[0] * 0x9E3779B1)) & 0xFFFFFFFFFFFFFFFF
+    return _seed_at(_seed_counter[0])
+
+
+class SeedLease(object):
+    """The seeds of the draws `start + 1, start + 2, ...` of the per-launch sequence, handed out AHEAD of their turn: a block of launches that is
+    issued earlier than its place in the call order (an encoder stack run beside another one, training/detr_transformer.py) draws from the lease
+    (`with lease:`), and `redeem()` at its old place moves the sequence past the leased draws -- if the sequence stands where the lease started.
+    Every launch then carries the seed it carries when the block is issued in place."""
+
+    def __init__(self, start):
+        self.start, self.drawn = start, 0
+
+    def draw(self):
+        self.drawn += 1
+        return _seed_at(self.start + self.drawn)
+
+    def __enter__(self):
+        assert _seed_lease[0] is None
+        _seed_lease[0] = self
+        return self
+
+    def __exit__(self, *exc):
+        _seed_lease[0] = None
+        return False
+
+    def redeem(self):
+        """-> True and the sequence moved past the leased draws, or False (the sequence is somewhere else: the block has to be issued again, in place)."""
+        if _seed_counter[0] != self.start:
+            return False
+        _seed_counter[0] += self.drawn
+        return True
+
+
+_seed_lease = [None]
+
+
+def seed_position():
+    """Number of per-launch seeds drawn so far."""
+    return _seed_counter[0]
 
 
 _iter_seed = {}
@@ -252,6 +301,8 @@ def epilogue(alpha=1.0, col_scale=None, col_bias=None, samp_scale=None, residual
     ep.seed_ptr = iter_seed().data_ptr() if p_drop > 0 else None
     ep.accumulate = 1 if accumulate else 0
     ep.a_rowsum = a_rowsum.data_ptr() if a_rowsum is not None else None
+    if _rider is not None and _rider.MODE == 'record':
+        ep._keep = (col_scale, col_bias, samp_scale, residual, mask_src, a_rowsum)      # a queued launch keeps what its epilogue points at alive
     return ep
 
 
@@ -264,6 +315,9 @@ def gemm(A, B, ta, tb, M, N, K, out=None, ep=None, splitk=0, pix_per_sample=0, l
         out = torch.empty((M, N), device=A.device, dtype=torch.float32)
     lda = A.stride(0) if lda is None else lda
     ldb = B.stride(0) if ldb is None else ldb
+    if _rider is not None and _rider.MODE is not None and not ta and not tb and splitk == 0 and pix_per_sample == 0:
+        _rider.gemm(A, B, M, N, K, out, ep, lda, ldb)      # an encoder stack in lock-step with another one: queued, or sent with the other's launch
+        return out
     engine_call('gemm', 2.0 * M * N * K, lambda: check(lib().ldetr_gemm_f32(
         ptr(A), lda, int(ta), ptr(B), ldb, int(tb), ptr(out), out.stride(0), M, N, K, splitk,
         ctypes.byref(ep) if ep is not None else None, pix_per_sample, stream()), 'gemm'), nbytes=4.0 * (M * K + N * K + M * N))

@@ -52,6 +52,8 @@ class _LinearFn(torch.autograd.Function):
         if add_input is not None:          # y = f((x + add_input) W^T): the position embedding of q/k (no gradient for it)
             if add_input.requires_grad:
                 raise RuntimeError('linear: add_input is a constant (the sine position embedding); a learned embedding must be added by the caller')
+            if core._rider is not None:
+                core._rider.check_ready(x2, 'linear(add_input=)')      # an ATen add: not on a result that is still queued
             x2 = x2 + add_input.reshape(-1, K)
         w = core.f32c(weight.detach()[r0:r1])
         b = core.f32c(bias.detach()[r0:r1]) if bias is not None else None

@@ -7,6 +7,7 @@ Internals differ by design: activations are batch-first row-major [B*L, d] matri
 every projection / FFN is one f32-MFMA GEMM with fused bias/relu/dropout, attention is one fused
 kernel per call, and each `x = norm(x + dropout(sub(x)))` is one kernel.
 """
+import contextlib
 import copy
 from typing import Optional
 
@@ -14,6 +15,7 @@ import torch
 from torch import Tensor, nn
 
 from ..hip import composite, core
+from ..hip import rider as hrider
 from ..hip.attention import kpm_u8 as _mask_u8      # bool key-padding mask -> the uint8 form the attention kernels read (no launch for a contiguous mask)
 from ..hip.attention import grouped_kv, mha_cross_kv, mha_forward
 from ..hip import ffn as hffn
@@ -142,6 +144,22 @@ class TransformerEncoder(nn.Module):
         prog = hstacks.Prog('enc', self.layers, x2, B, L, _mask_u8(kpm), self.training)
         return prog if hstacks.usable(prog) else None
 
+    def forward(self, x2, B, L, kpm, pos2, want_pos=False, rider=None, lease=None, rider_lease=None):
+        """forward2d; with rider = (encoder module, its x2, B, L, kpm, pos2), an INDEPENDENT stack of the same geometry that needs no autograd graph
+        (hip.rider.eligible), both stacks advance in lock-step, one launch per step for both -> (this stack's result, the rider's).  This stack
+        builds its usual autograd nodes with the same saved tensors; the rider runs under no_grad and keeps nothing.  lease / rider_lease: a
+        hip.core.SeedLease the stack draws its dropout seeds from (a stack issued ahead of its place in the call order)."""
+        if rider is None:
+            with (lease if lease is not None else contextlib.nullcontext()):
+                return self.forward2d(x2, B, L, kpm, pos2, want_pos=want_pos)
+        enc, rx2, rB, rL, rkpm, rpos2 = rider
+        assert pos2 is not None and rpos2 is not None, 'the lock-step path is the position-embedded encoders\''
+        with torch.no_grad(), (rider_lease if rider_lease is not None else contextlib.nullcontext()), hrider.mode('record'):
+            other = enc.forward2d(rx2, rB, rL, rkpm, rpos2, want_pos=want_pos)
+        with (lease if lease is not None else contextlib.nullcontext()), hrider.mode('pair'):
+            mine = self.forward2d(x2, B, L, kpm, pos2, want_pos=want_pos)
+        return mine, other
+
     def forward2d(self, x2, B, L, kpm, pos2, want_pos=False):
         """want_pos (with pos2): also return x_out + pos2 (the decoder's cross-attention key input, detr_transformer.py:277), formed by
         the last layer's LayerNorm launch.  Between layers the position-embedded copy comes from the previous layer's norm2 as well:
@@ -156,6 +174,7 @@ class TransformerEncoder(nn.Module):
         for i, layer in enumerate(self.layers):
             emit = pos2 is not None and (i + 1 < n or (want_pos and self.norm is None))
             if pos2 is not None and xpos2 is None:
+                hrider.check_ready(x2, 'encoder layer input + pos')      # an ATen add: only ever on the stack's input while a stack is recorded
                 xpos2 = x2 + pos2
             r = layer.forward2d(x2, B, L, kpm, pos2, xpos2=xpos2, emit_pos=emit)
             x2, xpos2 = r if emit else (r, None)
@@ -209,6 +228,34 @@ def _rows_from_nchw(x):
     return x.permute(0, 2, 3, 1).reshape(B * h * w, C), h * w
 
 
+class EncoderPartner(object):
+    """The image encoder of ANOTHER module (encoder stack, src [B, C, h, w], mask, pos_embed) that depends on nothing the current module computes:
+    handed to the module whose encoder comes first in the call order (Transformer.forward(enc_partner=)), it is evaluated beside that encoder
+    (TransformerEncoder.forward(rider=)) and its (memory, memory + pos) is parked here until its own module collects it (enc_memory=).
+    Dropout: every launch keeps the seed of its old place in the call order.  plan[key] = the number of seed draws between the two encoders'
+    starts; the first pass of a configuration runs both encoders in place and measures it, later passes lease the partner's seeds ahead
+    (hip.core.SeedLease).  If the sequence is not where the lease expects it at collection, the parked memory is dropped, the encoder runs in place
+    and the next pass measures again."""
+
+    def __init__(self, encoder, src, mask, pos_embed, plan, key):
+        self.encoder, self.src, self.mask, self.pos_embed, self.plan, self.key = encoder, src, mask, pos_embed, plan, key
+        self.memory = self.lease = self.probe_start = None
+
+    def collect(self):
+        """-> the parked (memory, memory + pos), or None: the caller runs its encoder now."""
+        if self.memory is not None:
+            mem, lease = self.memory, self.lease
+            self.memory = self.lease = None
+            if lease.redeem():
+                return mem
+            self.plan.pop(self.key, None)
+            return None
+        if self.probe_start is not None:
+            self.plan[self.key] = core.seed_position() - self.probe_start
+            self.probe_start = None
+        return None
+
+
 class Transformer(nn.Module):
     _with_token = False
 
@@ -237,8 +284,37 @@ class Transformer(nn.Module):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
 
-    def forward(self, src, mask, pos_embed, tgt, tgt_key_padding_mask, decoder_mask=None, partner=None):
-        """partner (extension): a hip.stacks.Prog to run in lock-step with the decoder -> (hs, memory, partner's output)."""
+    def _encode(self, x2, bs, S, mem_kpm, pos2, enc_partner, enc_memory):
+        """The image encoder, alone or with the other module's (EncoderPartner) -> (memory, memory + pos)."""
+        if enc_memory is not None:
+            got = enc_memory.collect()
+            if got is not None:
+                return got
+        if enc_partner is None:
+            return self.encoder.forward2d(x2, bs, S, mem_kpm, pos2, want_pos=True)
+        p = enc_partner
+        start = core.seed_position()
+        px2, pS = _rows_from_nchw(p.src)
+        ppos2 = _rows_from_nchw(p.pos_embed)[0].contiguous()
+        pkpm, pbs = p.mask.flatten(1), p.src.shape[0]
+        gap = p.plan.get(p.key)
+        if gap is None or not hrider.eligible(self.encoder, p.encoder, x2.shape[0], px2.shape[0], profiled=core.PROF.enabled):
+            p.probe_start = start      # this pass measures the partner's place in the seed sequence; it runs in its place
+            return self.encoder.forward2d(x2, bs, S, mem_kpm, pos2, want_pos=True)
+        lease = core.SeedLease(start + gap)
+        if torch.is_grad_enabled() and (px2.requires_grad or any(q.requires_grad for q in p.encoder.parameters())):
+            # the partner is the trained stack (Dmain: D's encoder beside the no-grad generator's): it owns the launches, this one rides
+            other, mine = p.encoder(px2, pbs, pS, pkpm, ppos2, want_pos=True, rider=(self.encoder, x2, bs, S, mem_kpm, pos2), lease=lease)
+        else:
+            mine, other = self.encoder(x2, bs, S, mem_kpm, pos2, want_pos=True, rider=(p.encoder, px2, pbs, pS, pkpm, ppos2), rider_lease=lease)
+        p.memory, p.lease = other, lease
+        return mine
+
+    def forward(self, src, mask, pos_embed, tgt, tgt_key_padding_mask, decoder_mask=None, partner=None, enc_partner=None, enc_memory=None):
+        """partner (extension): a hip.stacks.Prog to run in lock-step with the decoder -> (hs, memory, partner's output).
+        enc_partner / enc_memory (extension): an EncoderPartner -- the module whose encoder runs FIRST in the call order passes it as enc_partner
+        (the other module's encoder is evaluated beside this one and its memory parked on the object), the other module as enc_memory (collects
+        the parked memory instead of running its encoder)."""
         if decoder_mask is not None:
             raise NotImplementedError('decoder_mask (tgt_mask) is never passed on the LayoutDETR path')
         bs, c, h, w = src.shape
@@ -246,7 +322,7 @@ class Transformer(nn.Module):
         pos2, _ = _rows_from_nchw(pos_embed)
         pos2 = pos2.contiguous()
         mem_kpm = mask.flatten(1)
-        mem2, mem_pos2 = self.encoder.forward2d(x2, bs, S, mem_kpm, pos2, want_pos=True)
+        mem2, mem_pos2 = self._encode(x2, bs, S, mem_kpm, pos2, enc_partner, enc_memory)
         if self._with_token:
             tgt = torch.cat([self.token.expand(-1, bs, -1), tgt], dim=0)
             tgt_key_padding_mask = torch.cat([self.token_mask.expand(bs, -1), tgt_key_padding_mask], dim=1)

@@ -13,7 +13,9 @@ from ..hip import composite, core
 
 from ..hip import losses as hl
 from ..metrics.metric_layoutnet import compute_alignment, compute_overlap, generalized_iou_loss, layout_losses_per_sample
+from ..hip import rider as hrider
 from .detr_backbone import ResNet50Body, dual_trunk_forward, trunk_body
+from .detr_transformer import Transformer
 
 
 def _masked_mse(a, b, valid):
@@ -55,6 +57,20 @@ def _detached(trunk_out):
     """A trunk output (Generator / Discriminator `trunk_out`) without its autograd graph."""
     feats, pos = trunk_out
     return [NestedTensor(f.tensors.detach(), f.mask, getattr(f, 'uniform', False)) for f in feats], [p.detach() for p in pos]
+
+
+def _staged(module):
+    body = trunk_body(module)
+    return getattr(body, 'stages', None) is not None
+
+
+def encoder_partner_applies(G, D, background, staged=False, higher_order=False):
+    """Whether D's image encoder may run beside G's in a main phase: both modules have the hooks, one background tensor (not a ragged list with
+    masks of its own), encoders of the same geometry (hip.rider.eligible: depth, width, heads, feed-forward size), a backward in one piece."""
+    gt, dt = getattr(G, 'transformer', None), getattr(D, 'enc_transformer', None)
+    if not (hasattr(D, 'encoder_partner') and isinstance(gt, Transformer) and isinstance(dt, Transformer) and isinstance(background, torch.Tensor)):
+        return False
+    return hrider.eligible(gt.encoder, dt.encoder, 1, 1, staged=staged, higher_order=higher_order)
 
 
 class Loss:
@@ -100,6 +116,8 @@ class StyleGAN2Loss(Loss):
         # (values only: D is frozen there) and both D passes of Dmain (with its autograd graph).  The iteration driver gets it from
         # precompute_D_trunk() before the phases and hands it to them (accumulate_gradients(trunks=)); without it the per-phase behaviour
         # above applies.
+        self.backward_staged = False      # set by training_loop.staged_backward while a phase whose backward runs in stages is evaluated
+        self._enc_plan = {}      # detr_transformer.EncoderPartner: the measured place of D's image encoder in each main phase's seed sequence
         self._reporting = report_fn is not None   # the sign() statistics cost a launch each: only formed when someone listens
         self.report = report_fn if report_fn is not None else (lambda name, value: None)
         self.last = {}
@@ -142,15 +160,20 @@ class StyleGAN2Loss(Loss):
             return None, None
         return self.G.trunk(background, body_out=outs[0]), self.D.trunk(background, body_out=outs[1])
 
-    def run_G(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, update_emas=False, trunk_out=None):
+    def run_G(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, update_emas=False, trunk_out=None,
+              enc_partner=None):
         kw = {} if trunk_out is None else dict(trunk_out=trunk_out)
+        if enc_partner is not None:
+            kw['enc_partner'] = enc_partner
         if not reconst:
             return self.G(z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, **kw)
         return self.G(z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst, **kw)
 
     def run_D(self, bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, blur_sigma=0, update_emas=False,
-              trunk_out=None):
+              trunk_out=None, enc_memory=None):
         kw = {} if trunk_out is None else dict(trunk_out=trunk_out)
+        if enc_memory is not None:
+            kw['enc_memory'] = enc_memory
         if not reconst:
             return self.D(bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, **kw)
         return self.D(bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, reconst, **kw)
@@ -162,9 +185,12 @@ class StyleGAN2Loss(Loss):
         valid = ~padding_mask
         static = bool(getattr(self.G, 'static_shapes', False))
         g_trunk, d_trunk = self.grouped_trunks(background) if trunks is None else (trunks[0], _detached(trunks[1]))
+        # D's image encoder needs nothing G computes (only D's decoder sees the generated boxes): it rides on G's, one launch per step for both
+        partner = self.encoder_partner('Gmain', d_trunk, background)
         bbox_fake, loss_z, cls_logits, loss_lm, loss_text_len = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c,
-                                                                           reconst=True, trunk_out=g_trunk)
-        gen_logits, gen_logits_uncond = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c, trunk_out=d_trunk)
+                                                                           reconst=True, trunk_out=g_trunk, enc_partner=partner)
+        gen_logits, gen_logits_uncond = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c, trunk_out=d_trunk,
+                                                   enc_memory=partner)
         T = hl.Term
         lay = None
         if static and bbox_fake.is_cuda and bbox_fake.shape[1] <= 64:
@@ -200,13 +226,25 @@ class StyleGAN2Loss(Loss):
         self.last = dict(bbox_fake=bbox_fake.detach(), **{k: v.detach() for k, v in rep.items()})
         return total
 
-    def _generate_for_D(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=None):
+    def encoder_partner(self, phase, d_trunk, background, pair=False):
+        """D's image encoder on its trunk output as the partner of G's in a main phase (detr_transformer.EncoderPartner: handed to G's forward, which
+        evaluates both encoders in lock-step, then to D's, which collects its memory), or None where the phases keep the two encoder passes apart:
+        no trunk output in hand, ragged backgrounds, a staged backward, a twice-differentiable regulariser pass, modules without the hooks,
+        LDETR_DEBUG="ENC_RIDER=0"."""
+        # staged: training_loop.staged_backward says so (backward_staged); a trunk body that is recording cuts says the same for drivers of their own
+        staged = self.backward_staged or _staged(self.G) or _staged(self.D)
+        if d_trunk is None or not encoder_partner_applies(self.G, self.D, background, staged=staged, higher_order=composite.active()):
+            return None
+        return self.D.encoder_partner(d_trunk, self._enc_plan, (phase, tuple(background.shape), self.G.training, self.D.training), pair=pair)
+
+    def _generate_for_D(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=None, enc_partner=None):
         """G's layouts for a D phase (loss.py:146-149) and D's trunk output on the backgrounds: `trunk_out` if given, else evaluated here grouped with
         G's trunk (grouped_trunks; None where that does not apply: D then evaluates its own) -> (bbox_fake, D's trunk_out)."""
         g_trunk = None
         if trunk_out is None:
             g_trunk, trunk_out = self.grouped_trunks(background)
-        bbox_fake = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True, trunk_out=g_trunk)
+        bbox_fake = self.run_G(gen_z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True, trunk_out=g_trunk,
+                               enc_partner=enc_partner)
         return bbox_fake, trunk_out
 
     def d_gen_terms(self, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c, trunk_out=None, gen_out=None):
@@ -330,12 +368,14 @@ class StyleGAN2Loss(Loss):
         if phase == 'Dmain':
             if self.share_D_trunk and hasattr(self.D, 'trunk'):   # True / 'phase' / 'iteration'
                 # the phase's one D-trunk evaluation (with the generator's no-grad trunk grouped beside it), unless the iteration's is handed in
+                # D's (trained, 2B-row) image encoder is evaluated beside the no-grad generator's; forward_pair collects its memory, graph included
+                partner = self.encoder_partner('Dmain', trunks[1], background, pair=True) if (trunks is not None and self.pair_D_passes) else None
                 bbox_fake, trunk = self._generate_for_D(bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_z, gen_c,
-                                                        None if trunks is None else trunks[1])
+                                                        None if trunks is None else trunks[1], enc_partner=partner)
                 if self.pair_D_passes:
                     # both D passes of the phase as ONE batch of 2B layouts (Discriminator.forward_pair): half the transformer / head launches
                     gen_out, real_out = self.D.forward_pair(bbox_fake, bbox_real.detach(), bbox_class, bbox_text, bbox_patch, padding_mask, background, real_c,
-                                                            trunk_out=trunk)
+                                                            trunk_out=trunk, **({} if partner is None else dict(enc_memory=partner)))
                 else:
                     trunk = trunk if trunk is not None else self.D.trunk(background)
                     gen_out = self.run_D(bbox_fake, bbox_class, bbox_text, bbox_patch, padding_mask, background, gen_c, update_emas=True, trunk_out=trunk)

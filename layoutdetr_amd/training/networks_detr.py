@@ -34,7 +34,7 @@ from ..hip import core
 from ..hip.linear import linear
 from .detr_backbone import Backbone, Joiner
 from .detr_position_encoding import PositionEmbeddingSine
-from .detr_transformer import Transformer, TransformerEncoder, TransformerEncoderLayer, TransformerWithToken
+from .detr_transformer import EncoderPartner, Transformer, TransformerEncoder, TransformerEncoderLayer, TransformerWithToken
 from .networks_stylegan2 import Decoder
 from .util import TransformerWithToken_layoutganpp, encode_seq_first, encode_seq_first_pair
 
@@ -337,7 +337,8 @@ class Generator(nn.Module):
         from . import shared_decode
         return shared_decode.decode_candidates(self, cond, z)
 
-    def forward(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, trunk_out=None):
+    def forward(self, z, bbox_class, bbox_real, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, trunk_out=None, enc_partner=None):
+        """enc_partner (extension): a detr_transformer.EncoderPartner -- the discriminator's image encoder, evaluated beside this module's."""
         bg_feat, pos = self.trunk(background) if trunk_out is None else trunk_out
         bg_feat, mask = bg_feat[-1].decompose()
         assert mask is not None
@@ -352,7 +353,7 @@ class Generator(nn.Module):
         x = torch.cat([zf, l, text_feat, text_len_feat], dim=-1)
         x = self.fc_in(x, final_relu=True).permute(1, 0, 2)
 
-        x = self.transformer(src=self.input_proj(bg_feat), mask=mask, pos_embed=pos[-1], tgt=x, tgt_key_padding_mask=padding_mask)[0]
+        x = self.transformer(src=self.input_proj(bg_feat), mask=mask, pos_embed=pos[-1], tgt=x, tgt_key_padding_mask=padding_mask, enc_partner=enc_partner)[0]
         bbox_fake = self.bbox_embed(x).sigmoid()
         if not reconst:
             return bbox_fake
@@ -441,7 +442,7 @@ class Discriminator(nn.Module):
             background = nested_tensor_from_tensor_list(background)
         return self.backbone(background, body_out)
 
-    def _logits(self, bbox, l, text_feat, text_len_feat, l_uncond, padding_mask, src, mask, pos):
+    def _logits(self, bbox, l, text_feat, text_len_feat, l_uncond, padding_mask, src, mask, pos, enc_memory=None):
         """The two discriminator scores of a batch of layouts: -> (x0, logit, x0_uncond, logit_uncond)."""
         b = self.fc_bbox(bbox)
         x = torch.cat([b, l, text_feat, text_len_feat], dim=-1)
@@ -452,10 +453,10 @@ class Discriminator(nn.Module):
         # of enc_transformer, one launch per sub-block step for both stacks (hip.stacks); the reference runs them one after the other.
         partner = None if composite.active() else self.enc_transformer_uncond.as_prog(x_uncond, padding_mask)
         if partner is not None:
-            x, _, y_uncond = self.enc_transformer(src=src, mask=mask, pos_embed=pos, tgt=x, tgt_key_padding_mask=padding_mask, partner=partner[0])
+            x, _, y_uncond = self.enc_transformer(src=src, mask=mask, pos_embed=pos, tgt=x, tgt_key_padding_mask=padding_mask, partner=partner[0], enc_memory=enc_memory)
             x_uncond = partner[1](y_uncond)
         else:
-            x = self.enc_transformer(src=src, mask=mask, pos_embed=pos, tgt=x, tgt_key_padding_mask=padding_mask)[0]
+            x = self.enc_transformer(src=src, mask=mask, pos_embed=pos, tgt=x, tgt_key_padding_mask=padding_mask, enc_memory=enc_memory)[0]
             x_uncond = self.enc_transformer_uncond(x_uncond, src_key_padding_mask=padding_mask)
         x0 = x.transpose(0, 1)[0]
         logit_disc = self.fc_out_disc(x0).squeeze(-1)
@@ -492,7 +493,17 @@ class Discriminator(nn.Module):
         logit_cls_uncond = self.fc_out_cls_uncond(x_uncond)
         return bbox_pred, logit_cls, loss_lm, loss_text_len, bg_rec, bbox_pred_uncond, logit_cls_uncond
 
-    def forward(self, bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, trunk_out=None):
+    def encoder_partner(self, trunk_out, plan, key, pair=False):
+        """This module's image encoder on a trunk output as a detr_transformer.EncoderPartner for the generator's forward (pair: the 2B-row input of
+        forward_pair) -> pass the same object to forward / forward_pair as enc_memory."""
+        bg_feat, pos = trunk_out
+        bg_feat, mask = bg_feat[-1].decompose()
+        src, pe = self.input_proj(bg_feat), pos[-1]
+        if pair:
+            src, mask, pe = torch.cat([src, src], dim=0), torch.cat([mask, mask], dim=0), torch.cat([pe, pe], dim=0)
+        return EncoderPartner(self.enc_transformer.encoder, src, mask, pe, plan, key)
+
+    def forward(self, bbox, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, reconst=False, trunk_out=None, enc_memory=None):
         bg_feat, pos = self.trunk(background) if trunk_out is None else trunk_out
         bg_feat, mask = bg_feat[-1].decompose()
         assert mask is not None
@@ -503,12 +514,13 @@ class Discriminator(nn.Module):
         text_feat, text_len = _text_inputs(self, bbox_text, B, N, bbox_class.device)
         text_len_feat = self.enc_text_len(text_len)
         x0, logit_disc, x0_uncond, logit_disc_uncond = self._logits(bbox, l, text_feat, text_len_feat, self.emb_label_uncond(bbox_class), padding_mask,
-                                                                    self.input_proj(bg_feat), mask, pos[-1])
+                                                                    enc_memory.src if enc_memory is not None else self.input_proj(bg_feat), mask, pos[-1],
+                                                                    enc_memory=enc_memory)
         if not reconst:
             return logit_disc, logit_disc_uncond
         return (logit_disc, logit_disc_uncond) + self._reconstruct(x0, x0_uncond, bbox_text, text_len, padding_mask, B, N)
 
-    def forward_pair(self, bbox_fake, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, trunk_out=None):
+    def forward_pair(self, bbox_fake, bbox_real, bbox_class, bbox_text, bbox_patch, padding_mask, background, c, trunk_out=None, enc_memory=None):
         """D(bbox_fake) and D(bbox_real, reconst=True) of the SAME layouts' conditions in one pass — what phase Dmain evaluates with two
         calls (training/loss.py:149,165).  The samples of a batch are independent (FrozenBatchNorm, no batch statistics), so the two
         score paths run as ONE batch of 2B layouts: trunk, input_proj, label / text embeddings and the text encoder are evaluated
@@ -524,6 +536,8 @@ class Discriminator(nn.Module):
         l_uncond = self.emb_label_uncond(bbox_class)
         two = lambda t: torch.cat([t, t], dim=0)
         x0, logit, x0_uncond, logit_uncond = self._logits(torch.cat([bbox_fake, bbox_real], dim=0), two(l), two(text_feat), two(text_len_feat), two(l_uncond),
-                                                            two(padding_mask), two(self.input_proj(bg_feat)), two(mask), two(pos[-1]))
+                                                            two(padding_mask), enc_memory.src if enc_memory is not None else two(self.input_proj(bg_feat)),
+                                                            enc_memory.mask if enc_memory is not None else two(mask),
+                                                            enc_memory.pos_embed if enc_memory is not None else two(pos[-1]), enc_memory=enc_memory)
         rec = self._reconstruct(x0[B:], x0_uncond[B:], bbox_text, text_len, padding_mask, B, N)
         return (logit[:B], logit_uncond[:B]), (logit[B:], logit_uncond[B:]) + rec

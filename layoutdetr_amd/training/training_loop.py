@@ -607,6 +607,9 @@ def staged_backward(loss, phase, dp, run_stage1, between=None, exchange=None, st
     if exchange is None:
         exchange = lambda ranges: [dp.exchange_async(phase.fm.gflat, lo, hi) for lo, hi in ranges]
     try:
+        # the loss is told, not left to find out: with handed-in `stages` (D's cuts recorded before the phases) nothing on the module shows that
+        # this phase's backward is staged (StyleGAN2Loss.encoder_partner keeps the two encoder passes apart then)
+        loss.backward_staged = True
         run_stage1()
         if between is not None:
             between(1)
@@ -617,6 +620,7 @@ def staged_backward(loss, phase, dp, run_stage1, between=None, exchange=None, st
                 between(i)
             exchange(segs[i - 1])
     finally:
+        loss.backward_staged = False
         body.stages = None
     return True
 
