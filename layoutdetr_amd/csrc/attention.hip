@@ -669,77 +669,63 @@ static int attn_fwd_route(const AttnParams& p, int head_dim, int* tmpl) {
     return 1;
 }
 
+// The one conversion of a forward argument block into kernel parameters, with the checks every forward entry makes (`what`: the entry called).
+static int attn_fwd_params(const ldetr_attn_args& a, const char* what, AttnParams* p) {
+    LDETR_CHECK(a.head_dim >= 32 && a.head_dim <= 192 && a.head_dim % 32 == 0, "%s: head_dim must be a multiple of 32 up to 192 (got %d)", what, a.head_dim);
+    memset(p, 0, sizeof(*p));
+    p->q = a.q; p->k = a.k; p->v = a.v; p->ldq = a.ldq; p->ldk = a.ldk; p->ldv = a.ldv; p->kpm = a.key_padding_mask;
+    p->o = a.out; p->ldo = a.ldo; p->lse = a.lse; p->B = a.B; p->H = a.H; p->Lq = a.Lq; p->Lk = a.Lk;
+    p->scale = a.scale; p->p_drop = a.p_drop; p->seed = a.seed; p->seed_ptr = (const unsigned long long*)a.seed_ptr; p->causal = a.causal;
+    LDETR_CHECK(!a.causal || a.Lq == a.Lk, "%s: the causal mask is defined for self-attention (Lq == Lk)", what);
+    return check_attn(*p, what);
+}
+
+// The instantiation ladders of the forward kernels, written once for their one- and two-problem forms: f(AttnInt<N>()), which launches the kernel
+// that has N for its template argument, for the first N of the ladder that is >= v (the last one otherwise).
+template <int N> struct AttnInt { static constexpr int value = N; };
+template <int N, int... REST, typename F>
+static void attn_ladder(int v, F f) {
+    if constexpr (sizeof...(REST) == 0) f(AttnInt<N>());
+    else if (v <= N) f(AttnInt<N>());
+    else attn_ladder<REST...>(v, f);
+}
+// key tiles of attn_fwd_kernel / attn_fwd_pair_kernel, 64-key chunks of attn_fwd_wide_kernel / attn_fwd_wide_pair_kernel (attn_fwd_route's *tmpl), 32-wide head chunks
+template <typename F> static void attn_key_tiles(int tmpl, F f) { attn_ladder<1, 2, 4, 8, 16>(tmpl, f); }
+template <typename F> static void attn_key_chunks(int nch, F f) { attn_ladder<1, 2, 3, 4>(nch, f); }
+template <typename F> static void attn_head_chunks(int head_dim, F f) { attn_ladder<1, 2, 3, 4, 5, 6>(head_dim / 32, f); }
+constexpr size_t attn_wide_lds(int dhc) { return (size_t)64 * (32 * dhc + 4) * sizeof(float); }
+
+// One problem: the launch of both forward entries (the group entry's n == 1).
+static int attn_fwd_one(const ldetr_attn_args& a, const char* what, hipStream_t st) {
+    AttnParams p;
+    int rc = attn_fwd_params(a, what, &p);
+    if (rc) return rc;
+    const int grid = p.B * p.H * ((p.Lq + 15) / 16);
+    int tmpl = 0;
+    const int route = attn_fwd_route(p, a.head_dim, &tmpl);
+    if (route == 0) {     // long key sequences: chunked online softmax
+        attn_head_chunks(a.head_dim, [&](auto D) { hipLaunchKernelGGL((attn_fwd_long_kernel<D.value>), grid, 64, 0, st, p); });
+        return check_launch("attention_fwd_long");
+    }
+    if (route == 2) {     // wide kernel: LDS-staged K / V shared by four query tiles per block (attn_fwd_route)
+        const int wgrid = p.B * p.H * ((p.Lq + 63) / 64);
+        attn_head_chunks(a.head_dim, [&](auto D) {
+            attn_key_chunks(tmpl, [&](auto T) { hipLaunchKernelGGL((attn_fwd_wide_kernel<T.value, D.value>), wgrid, 256, attn_wide_lds(D.value), st, p); });
+        });
+        return check_launch("attention_fwd_wide");
+    }
+    attn_head_chunks(a.head_dim, [&](auto D) {
+        attn_key_tiles(tmpl, [&](auto T) { hipLaunchKernelGGL((attn_fwd_kernel<T.value, D.value>), grid, 64, 0, st, p); });
+    });
+    return check_launch("attention_fwd");
+}
+
 extern "C" int ldetr_attention_fwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                                        const unsigned char* key_padding_mask, float* out, int64_t ldo, float* lse,
                                        int B, int H, int Lq, int Lk, int head_dim, float scale,
                                        float p_drop, uint64_t seed, const uint64_t* seed_ptr, int causal, void* stream) {
-    LDETR_CHECK(head_dim >= 32 && head_dim <= 192 && head_dim % 32 == 0, "attention_fwd: head_dim must be a multiple of 32 up to 192 (got %d)", head_dim);
-    AttnParams p; memset(&p, 0, sizeof(p));
-    p.q = q; p.k = k; p.v = v; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.kpm = key_padding_mask;
-    p.o = out; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk;
-    p.scale = scale; p.p_drop = p_drop; p.seed = seed; p.seed_ptr = (const unsigned long long*)seed_ptr; p.causal = causal;
-    LDETR_CHECK(!causal || Lq == Lk, "attention_fwd: the causal mask is defined for self-attention (Lq == Lk)");
-    int rc = check_attn(p, "attention_fwd");
-    if (rc) return rc;
-    const int nqt = (Lq + 15) / 16;
-    const int grid = B * H * nqt;
-    hipStream_t st = (hipStream_t)stream;
-    int tmpl = 0;
-    const int route = attn_fwd_route(p, head_dim, &tmpl);
-#define LDETR_ATTN_FWD(DHC)                                                                     \
-    do {                                                                                         \
-        if (tmpl == 1) hipLaunchKernelGGL((attn_fwd_kernel<1, DHC>), grid, 64, 0, st, p);        \
-        else if (tmpl == 2) hipLaunchKernelGGL((attn_fwd_kernel<2, DHC>), grid, 64, 0, st, p);   \
-        else if (tmpl == 4) hipLaunchKernelGGL((attn_fwd_kernel<4, DHC>), grid, 64, 0, st, p);   \
-        else if (tmpl == 8) hipLaunchKernelGGL((attn_fwd_kernel<8, DHC>), grid, 64, 0, st, p);   \
-        else hipLaunchKernelGGL((attn_fwd_kernel<16, DHC>), grid, 64, 0, st, p);                 \
-    } while (0)
-    if (route == 0) {     // long key sequences: chunked online softmax
-        switch (head_dim / 32) {
-            case 1: hipLaunchKernelGGL((attn_fwd_long_kernel<1>), grid, 64, 0, st, p); break;
-            case 2: hipLaunchKernelGGL((attn_fwd_long_kernel<2>), grid, 64, 0, st, p); break;
-            case 3: hipLaunchKernelGGL((attn_fwd_long_kernel<3>), grid, 64, 0, st, p); break;
-            case 4: hipLaunchKernelGGL((attn_fwd_long_kernel<4>), grid, 64, 0, st, p); break;
-            case 5: hipLaunchKernelGGL((attn_fwd_long_kernel<5>), grid, 64, 0, st, p); break;
-            default: hipLaunchKernelGGL((attn_fwd_long_kernel<6>), grid, 64, 0, st, p); break;
-        }
-        return check_launch("attention_fwd_long");
-    }
-    // wide kernel: LDS-staged K / V shared by four query tiles per block (attn_fwd_route)
-    if (route == 2) {
-        const int nch = tmpl, wgrid = B * H * ((Lq + 63) / 64);
-#define LDETR_ATTN_WIDE(NCH, DHC)                                                                                         \
-    do {                                                                                                                   \
-        constexpr size_t lds = (size_t)64 * (32 * DHC + 4) * sizeof(float);                                                \
-        hipLaunchKernelGGL((attn_fwd_wide_kernel<NCH, DHC>), wgrid, 256, lds, st, p);                                      \
-    } while (0)
-#define LDETR_ATTN_WIDE_D(DHC)                                                                                            \
-    do {                                                                                                                   \
-        if (nch <= 1) LDETR_ATTN_WIDE(1, DHC); else if (nch <= 2) LDETR_ATTN_WIDE(2, DHC);                                 \
-        else if (nch <= 3) LDETR_ATTN_WIDE(3, DHC); else LDETR_ATTN_WIDE(4, DHC);                                          \
-    } while (0)
-        switch (head_dim / 32) {
-            case 1: LDETR_ATTN_WIDE_D(1); break;
-            case 2: LDETR_ATTN_WIDE_D(2); break;
-            case 3: LDETR_ATTN_WIDE_D(3); break;
-            case 4: LDETR_ATTN_WIDE_D(4); break;
-            case 5: LDETR_ATTN_WIDE_D(5); break;
-            default: LDETR_ATTN_WIDE_D(6); break;
-        }
-#undef LDETR_ATTN_WIDE_D
-#undef LDETR_ATTN_WIDE
-        return check_launch("attention_fwd_wide");
-    }
-    switch (head_dim / 32) {
-        case 1: LDETR_ATTN_FWD(1); break;
-        case 2: LDETR_ATTN_FWD(2); break;
-        case 3: LDETR_ATTN_FWD(3); break;
-        case 4: LDETR_ATTN_FWD(4); break;
-        case 5: LDETR_ATTN_FWD(5); break;
-        default: LDETR_ATTN_FWD(6); break;
-    }
-#undef LDETR_ATTN_FWD
-    return check_launch("attention_fwd");
+    const ldetr_attn_args a = {q, ldq, k, ldk, v, ldv, key_padding_mask, out, ldo, lse, B, H, Lq, Lk, head_dim, scale, p_drop, seed, seed_ptr, causal};
+    return attn_fwd_one(a, "attention_fwd", (hipStream_t)stream);
 }
 
 // Two independent attention problems (32-wide heads) as ONE launch: problem 1's blocks follow problem 0's in the grid and every block runs the body
@@ -748,50 +734,31 @@ extern "C" int ldetr_attention_fwd_f32(const float* q, int64_t ldq, const float*
 // one, or have wider heads): the caller issues them singly.
 extern "C" int ldetr_attention_fwd_group_f32(const ldetr_attn_args* a, int n, void* stream) {
     LDETR_CHECK(a && (n == 1 || n == 2), "attention_fwd_group: 1 or 2 problems");
-    if (n == 1)
-        return ldetr_attention_fwd_f32(a->q, a->ldq, a->k, a->ldk, a->v, a->ldv, a->key_padding_mask, a->out, a->ldo, a->lse, a->B, a->H, a->Lq, a->Lk,
-                                       a->head_dim, a->scale, a->p_drop, a->seed, a->seed_ptr, a->causal, stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 1) return attn_fwd_one(a[0], "attention_fwd_group", st);
     AttnParams p[2];
     int route[2], tmpl[2] = {0, 0};
     for (int i = 0; i < 2; i++) {
-        const ldetr_attn_args& s = a[i];
-        if (s.head_dim != 32) {
-            set_error("attention_fwd_group: 32-wide heads only (problem %d has %d)", i, s.head_dim);
+        if (a[i].head_dim != 32) {
+            set_error("attention_fwd_group: 32-wide heads only (problem %d has %d)", i, a[i].head_dim);
             return LDETR_ERR_UNSUPPORTED;
         }
-        AttnParams& q = p[i]; memset(&q, 0, sizeof(q));
-        q.q = s.q; q.k = s.k; q.v = s.v; q.ldq = s.ldq; q.ldk = s.ldk; q.ldv = s.ldv; q.kpm = s.key_padding_mask;
-        q.o = s.out; q.ldo = s.ldo; q.lse = s.lse; q.B = s.B; q.H = s.H; q.Lq = s.Lq; q.Lk = s.Lk;
-        q.scale = s.scale; q.p_drop = s.p_drop; q.seed = s.seed; q.seed_ptr = (const unsigned long long*)s.seed_ptr; q.causal = s.causal;
-        LDETR_CHECK(!s.causal || s.Lq == s.Lk, "attention_fwd_group: the causal mask is defined for self-attention (Lq == Lk)");
-        int rc = check_attn(q, "attention_fwd_group");
+        int rc = attn_fwd_params(a[i], "attention_fwd_group", &p[i]);
         if (rc) return rc;
-        route[i] = attn_fwd_route(q, s.head_dim, &tmpl[i]);
+        route[i] = attn_fwd_route(p[i], 32, &tmpl[i]);
     }
     if (route[0] == 0 || route[0] != route[1] || tmpl[0] != tmpl[1]) {
         set_error("attention_fwd_group: the problems resolve to different kernels");
         return LDETR_ERR_UNSUPPORTED;
     }
-    hipStream_t st = (hipStream_t)stream;
+    // query rows per block: 64 in the wide kernel, 16 in the other
+    const int rows = route[0] == 2 ? 64 : 16;
+    const int nb0 = p[0].B * p[0].H * ((p[0].Lq + rows - 1) / rows), nb1 = p[1].B * p[1].H * ((p[1].Lq + rows - 1) / rows);
     if (route[0] == 2) {
-        const int nb0 = p[0].B * p[0].H * ((p[0].Lq + 63) / 64), nb1 = p[1].B * p[1].H * ((p[1].Lq + 63) / 64);
-        constexpr size_t lds = (size_t)64 * (32 + 4) * sizeof(float);
-        switch (tmpl[0]) {
-            case 1: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<1, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
-            case 2: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<2, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
-            case 3: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<3, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
-            default: hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<4, 1>), nb0 + nb1, 256, lds, st, p[0], p[1], nb0); break;
-        }
+        attn_key_chunks(tmpl[0], [&](auto T) { hipLaunchKernelGGL((attn_fwd_wide_pair_kernel<T.value, 1>), nb0 + nb1, 256, attn_wide_lds(1), st, p[0], p[1], nb0); });
         return check_launch("attention_fwd_wide_pair");
     }
-    const int nb0 = p[0].B * p[0].H * ((p[0].Lq + 15) / 16), nb1 = p[1].B * p[1].H * ((p[1].Lq + 15) / 16);
-    switch (tmpl[0]) {
-        case 1: hipLaunchKernelGGL((attn_fwd_pair_kernel<1, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
-        case 2: hipLaunchKernelGGL((attn_fwd_pair_kernel<2, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
-        case 4: hipLaunchKernelGGL((attn_fwd_pair_kernel<4, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
-        case 8: hipLaunchKernelGGL((attn_fwd_pair_kernel<8, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
-        default: hipLaunchKernelGGL((attn_fwd_pair_kernel<16, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); break;
-    }
+    attn_key_tiles(tmpl[0], [&](auto T) { hipLaunchKernelGGL((attn_fwd_pair_kernel<T.value, 1>), nb0 + nb1, 64, 0, st, p[0], p[1], nb0); });
     return check_launch("attention_fwd_pair");
 }
 

@@ -1450,12 +1450,6 @@ static int small_split_factor(int K, long blocks) {   // the rule alone: nothing
     return sk;
 }
 
-static int plan_small_split(GemmParams& p, long blocks) {
-    int sk = small_split_factor(p.K, blocks);
-    if (sk > 1 && !ring_alloc(blocks, (size_t)blocks * sk * 1024 * sizeof(float), &p.ws_count, &p.ws)) sk = 1;
-    return sk;
-}
-
 static bool small_fast_ok(const GemmParams& p, int ta, int tb) {
     static const int on = (int)knob("SMALL_FAST", 1);
     const long a_bytes = (ta ? (long)p.K * p.A.ld : (long)p.M * p.A.ld) * 4, b_bytes = (tb ? (long)p.K * p.B.ld : (long)p.N * p.B.ld) * 4;
@@ -1466,13 +1460,36 @@ static bool small_fast_ok(const GemmParams& p, int ta, int tb) {
 // 8 waves per block: few blocks, each with a long reduction of its own
 static bool small_wants8(long blocks, int sk, int K) { return blocks * sk <= 256 && (K + sk - 1) / sk >= 512; }
 
-// The small-tile kernels by operand modes: (TA, TB) -> gemm_small_kernel, (TA0, TB0, TA1, TB1) -> gemm_small_pair_kernel.
+// The launch plan of ONE small-tile problem, whatever launch form carries it (single, pair, pair-forward, group): gx tiles across, nt tiles in
+// all, sk reduction slices per tile, and the (FAST, 8-wave) instantiation the problem takes on its own.
+struct SmallPlan { int gx, nt, sk; bool fast, w8; };
+
+static SmallPlan small_plan_rule(const GemmParams& p, int ta, int tb) {   // the rule alone: nothing is allocated
+    SmallPlan s;
+    s.gx = cdiv(p.N, 32); s.nt = s.gx * cdiv(p.M, 32);
+    s.sk = small_split_factor(p.K, s.nt);
+    s.fast = small_fast_ok(p, ta, tb);
+    s.w8 = small_wants8(s.nt, s.sk, p.K);
+    return s;
+}
+
+// Takes a split plan's slice of the rings (counters + partial tiles); a split the rings cannot serve becomes the unsplit plan, with its wave count.
+static void small_plan_commit(GemmParams& p, SmallPlan& s) {
+    if (s.sk > 1 && !ring_alloc(s.nt, (size_t)s.nt * s.sk * 1024 * sizeof(float), &p.ws_count, &p.ws)) {
+        s.sk = 1;
+        s.w8 = small_wants8(s.nt, 1, p.K);
+    }
+}
+
+// The small-tile kernels by operand modes: (TA, TB) -> gemm_small_kernel, (TA0, TB0, TA1, TB1) -> gemm_small_pair_kernel, () -> gemm_small_group_kernel.
 template <int NW, bool FAST, int TA, int TB>
 static auto small_kernel() { return gemm_small_kernel<TA, TB, NW, FAST>; }
 template <int NW, bool FAST, int TA0, int TB0, int TA1, int TB1>
 static auto small_kernel() { return gemm_small_pair_kernel<TA0, TB0, TA1, TB1, NW, FAST>; }
+template <int NW, bool FAST>
+static auto small_kernel() { return gemm_small_group_kernel<NW, FAST>; }
 
-// One launch ladder for both: the FAST (scalar-addressed loads) x 8-wave instantiation of the kernel MODES names.
+// One launch ladder for all three: the FAST (scalar-addressed loads) x 8-wave instantiation of the kernel MODES names.
 template <int... MODES, typename... Args>
 static void launch_small_kernel(bool fast, bool w8, dim3 grid, hipStream_t st, const Args&... args) {
     if (fast) {
@@ -1487,29 +1504,24 @@ static void launch_small_kernel(bool fast, bool w8, dim3 grid, hipStream_t st, c
 
 template <int TA, int TB>
 static int launch_small(GemmParams& p, hipStream_t st) {
-    dim3 grid(cdiv(p.N, 32), cdiv(p.M, 32), 1);
-    const long blocks = (long)grid.x * grid.y;
-    const int sk = plan_small_split(p, blocks);
-    grid.z = sk;
-    const bool fast = small_fast_ok(p, TA, TB);
-    const bool w8 = small_wants8(blocks, sk, p.K);
-    launch_small_kernel<TA, TB>(fast, w8, grid, st, p);
-    note_engine_launch(2, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, sk, blocks * sk, TA * 2 + TB);
+    SmallPlan s = small_plan_rule(p, TA, TB);
+    small_plan_commit(p, s);
+    const dim3 grid(s.gx, s.nt / s.gx, s.sk);
+    launch_small_kernel<TA, TB>(s.fast, s.w8, grid, st, p);
+    note_engine_launch(2, 32, 32, 0, s.w8 ? 8 : 4, s.fast ? 1 : 0, 0, s.sk, (long)s.nt * s.sk, TA * 2 + TB);
     return check_launch("gemm_small");
 }
 
-// Two small-tile problems as ONE launch (gemm_small_pair_kernel): (TA0, 1) + (1, 1); each problem may carry its own in-kernel split-K.
-template <int TA0>
-static int launch_small_pair(GemmParams& p0, GemmParams& p1, hipStream_t st) {
-    const int gx0 = cdiv(p0.N, 32), nt0 = gx0 * cdiv(p0.M, 32), gx1 = cdiv(p1.N, 32), nt1 = gx1 * cdiv(p1.M, 32);
-    const int sk0 = plan_small_split(p0, nt0), sk1 = plan_small_split(p1, nt1);
-    // one block size for both: 8 waves only when both problems would take them on their own
-    const bool w8 = small_wants8(nt0, sk0, p0.K) && small_wants8(nt1, sk1, p1.K);
-    const bool fast = small_fast_ok(p0, TA0, 1) && small_fast_ok(p1, 1, 1);
-    const dim3 grid((unsigned)(nt0 * sk0 + nt1 * sk1));
-    launch_small_kernel<TA0, 1, 1, 1>(fast, w8, grid, st, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-    note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, sk0 * 256 + sk1, (long)grid.x, (TA0 * 2 + 1) * 4 + 3);
-    return check_launch("gemm_small_pair");
+// Two committed small-tile plans as ONE launch of gemm_small_pair_kernel<TA0, TB0, TA1, TB1>: problem 1's blocks follow problem 0's in the grid, each
+// problem with its own in-kernel split-K.  One instantiation for both: 8 waves only when both problems would take them on their own, FAST only when
+// both are (the forward pair has refused plans that differ by then).
+template <int TA0, int TB0, int TA1, int TB1>
+static int launch_small_pair(GemmParams& p0, const SmallPlan& s0, GemmParams& p1, const SmallPlan& s1, const char* what, hipStream_t st) {
+    const bool fast = s0.fast && s1.fast, w8 = s0.w8 && s1.w8;
+    const dim3 grid((unsigned)(s0.nt * s0.sk + s1.nt * s1.sk));
+    launch_small_kernel<TA0, TB0, TA1, TB1>(fast, w8, grid, st, p0, p1, s0.gx, s0.nt, s0.sk, s1.gx, s1.nt, s1.sk);
+    note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, s0.sk * 256 + s1.sk, (long)grid.x, (TA0 * 2 + TB0) * 4 + TA1 * 2 + TB1);
+    return check_launch(what);
 }
 
 // Second phase of a split-K contraction: C holds sum_k (already scaled by alpha); apply the rest of the epilogue in place.
@@ -1983,7 +1995,11 @@ extern "C" int ldetr_gemm_pair_f32(const ldetr_gemm_desc* g0, const ldetr_gemm_d
     LDETR_CHECK(g0 && g1, "gemm_pair: null descriptor");
     if (pair_single_launch(g0, g1)) {   // (an NN first problem carries no row-sum output here: pair_single_launch)
         GemmParams p0 = fill_dense(*g0), p1 = fill_dense(*g1);
-        return g0->ta == 1 ? launch_small_pair<1>(p0, p1, (hipStream_t)stream) : launch_small_pair<0>(p0, p1, (hipStream_t)stream);
+        SmallPlan s0 = small_plan_rule(p0, g0->ta, 1), s1 = small_plan_rule(p1, 1, 1);
+        small_plan_commit(p0, s0);
+        small_plan_commit(p1, s1);
+        hipStream_t st = (hipStream_t)stream;
+        return g0->ta == 1 ? launch_small_pair<1, 1, 1, 1>(p0, s0, p1, s1, "gemm_small_pair", st) : launch_small_pair<0, 1, 1, 1>(p0, s0, p1, s1, "gemm_small_pair", st);
     }
     int rc = gemm_dense(*g0, stream);
     if (rc) return rc;
@@ -2008,29 +2024,25 @@ extern "C" int ldetr_gemm_pair_fwd_f32(const ldetr_gemm_desc* g0, const ldetr_ge
         }
     }
     GemmParams p0 = fill_dense(*g0), p1 = fill_dense(*g1);
-    const int gx0 = cdiv(p0.N, 32), nt0 = gx0 * cdiv(p0.M, 32), gx1 = cdiv(p1.N, 32), nt1 = gx1 * cdiv(p1.M, 32);
-    const bool fast = small_fast_ok(p0, 0, 0);
-    if (fast != small_fast_ok(p1, 0, 0)) {
+    SmallPlan s0 = small_plan_rule(p0, 0, 0), s1 = small_plan_rule(p1, 0, 0);
+    if (s0.fast != s1.fast) {
         set_error("gemm_pair_fwd: the problems resolve to different instantiations (FAST)");
         return LDETR_ERR_UNSUPPORTED;
     }
-    // the wave counts are compared on the split factors of the rule alone first, so that a refused pair has taken no workspace slice
-    if (small_wants8(nt0, small_split_factor(p0.K, nt0), p0.K) != small_wants8(nt1, small_split_factor(p1.K, nt1), p1.K)) {
+    // the wave counts are compared on the plans of the rule alone first, so that a refused pair has taken no workspace slice
+    if (s0.w8 != s1.w8) {
         set_error("gemm_pair_fwd: the problems resolve to different instantiations (waves)");
         return LDETR_ERR_UNSUPPORTED;
     }
-    const int sk0 = plan_small_split(p0, nt0), sk1 = plan_small_split(p1, nt1);
-    const bool w8 = small_wants8(nt0, sk0, p0.K);
-    if (w8 != small_wants8(nt1, sk1, p1.K)) {
+    small_plan_commit(p0, s0);
+    small_plan_commit(p1, s1);
+    if (s0.w8 != s1.w8) {
         // (only when the workspace could not serve one of the two splits: the slice the other half took is left to the ring, which is harmless --
         // the single launches that follow take fresh ones)
         set_error("gemm_pair_fwd: the problems resolve to different instantiations (waves, one split without workspace)");
         return LDETR_ERR_UNSUPPORTED;
     }
-    const dim3 grid((unsigned)(nt0 * sk0 + nt1 * sk1));
-    launch_small_kernel<0, 0, 0, 0>(fast, w8, grid, (hipStream_t)stream, p0, p1, gx0, nt0, sk0, gx1, nt1, sk1);
-    note_engine_launch(3, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, sk0 * 256 + sk1, (long)grid.x, 0);
-    return check_launch("gemm_small_pair_fwd");
+    return launch_small_pair<0, 0, 0, 0>(p0, s0, p1, s1, "gemm_small_pair_fwd", (hipStream_t)stream);
 }
 
 // The grouped launch of NN problems: every problem must take, on its own, the unsplit small-tile kernel with the same (waves, FAST) pair.
@@ -2039,7 +2051,7 @@ static int launch_small_group(const ldetr_gemm_desc* d, const float* post_scale,
     g.n = n;
     fill_epilogue(g.ep0, nullptr);
     long total = 0;
-    bool fast = false, w8 = false;
+    SmallPlan first = {};
     for (int i = 0; i < n; i++) {
         const ldetr_gemm_desc& q = d[i];
         LDETR_CHECK(q.A && q.B && q.C, "gemm_small_group: null pointer (problem %d)", i);
@@ -2051,16 +2063,16 @@ static int launch_small_group(const ldetr_gemm_desc* d, const float* post_scale,
             set_error("gemm_small_group: problem %d is not a plain NN small-tile problem", i);
             return LDETR_ERR_UNSUPPORTED;
         }
-        const long blocks = (long)cdiv(q.N, 32) * cdiv(q.M, 32);
-        if (blocks <= 128 && q.K >= 1024) {   // (plan_small_split would split it)
+        ldetr_gemm_desc one = q; one.pix_per_sample = 0;
+        const GemmParams p = fill_dense(one);
+        const SmallPlan s = small_plan_rule(p, 0, 0);
+        // sk > 1 is small_split_factor's own condition, tiles <= 128 && K >= 1024: under it the rule gives sk >= 4 (K / 256 >= 4 and 128 x 4 <= 640)
+        if (s.sk > 1) {
             set_error("gemm_small_group: problem %d splits its reduction", i);
             return LDETR_ERR_UNSUPPORTED;
         }
-        ldetr_gemm_desc one = q; one.pix_per_sample = 0;
-        const GemmParams p = fill_dense(one);
-        const bool f = small_fast_ok(p, 0, 0), w = small_wants8(blocks, 1, p.K);
-        if (i == 0) { fast = f; w8 = w; }
-        else if (f != fast || w != w8) {
+        if (i == 0) first = s;
+        else if (s.fast != first.fast || s.w8 != first.w8) {
             set_error("gemm_small_group: problem %d resolves to another instantiation than problem 0", i);
             return LDETR_ERR_UNSUPPORTED;
         }
@@ -2070,19 +2082,11 @@ static int launch_small_group(const ldetr_gemm_desc* d, const float* post_scale,
         o.lda = (int)q.lda; o.ldb = (int)q.ldb; o.ldc = (int)q.ldc; o.avec = p.A.vec; o.bvec = p.B.vec; o.M = q.M; o.N = q.N; o.K = q.K;
         o.alpha = p.ep.alpha; o.post = post_scale ? post_scale[i] : 1.f;
         g.start[i] = (int)total;
-        total += blocks;
+        total += s.nt;
     }
     g.start[n] = (int)total;
-    const dim3 grid((unsigned)total);
-    if (fast) {
-        if (w8) hipLaunchKernelGGL((gemm_small_group_kernel<8, true>), grid, 512, 0, st, g);
-        else hipLaunchKernelGGL((gemm_small_group_kernel<4, true>), grid, 256, 0, st, g);
-    } else {
-        if (w8) hipLaunchKernelGGL((gemm_small_group_kernel<8, false>), grid, 512, 0, st, g);
-        else hipLaunchKernelGGL((gemm_small_group_kernel<4, false>), grid, 256, 0, st, g);
-    }
-    t_launches_f32++;
-    note_engine_launch(7, 32, 32, 0, w8 ? 8 : 4, fast ? 1 : 0, 0, 1, total, 0);
+    launch_small_kernel<>(first.fast, first.w8, dim3((unsigned)total), st, g);
+    note_engine_launch(7, 32, 32, 0, first.w8 ? 8 : 4, first.fast ? 1 : 0, 0, 1, total, 0);
     return check_launch("gemm_small_group");
 }
 

@@ -6,12 +6,33 @@
 head-averaged attention weights the reference discards (`[0]`) are never formed.
 Layout is batch-first: activations are [B*L, d] row-major (row = b*L + position).
 """
+import ctypes
 import math
 
 import torch
 
+from .. import _lib
 from . import core, rider
 from .linear import linear
+
+
+def _fwd_args(q, k, v, kpm, out, lse, B, H, Lq, Lk, dh, scale, p_drop, seed, causal):
+    """ldetr_attn_args of one forward problem: the ONE place that assigns its fields.  The block holds its tensors (`_keep`), so a queued one
+    (hip.rider) keeps them alive."""
+    a = _lib.AttnArgs()
+    a.q, a.ldq, a.k, a.ldk, a.v, a.ldv = q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0)
+    a.key_padding_mask = kpm.data_ptr() if kpm is not None else None
+    a.out, a.ldo, a.lse = out.data_ptr(), out.stride(0), lse.data_ptr()
+    a.B, a.H, a.Lq, a.Lk, a.head_dim, a.scale, a.p_drop, a.seed = B, H, Lq, Lk, dh, scale, p_drop, seed
+    a.seed_ptr = core.iter_seed().data_ptr() if p_drop > 0 else None
+    a.causal = causal
+    a._keep = (q, k, v, kpm, out, lse)
+    return a
+
+
+def _fwd(a):
+    """One forward problem as its own launch (the group entry's n == 1)."""
+    core.check(core.lib().ldetr_attention_fwd_group_f32(ctypes.byref(a), 1, core.stream()), 'attention_fwd')
 
 
 class _AttnFn(torch.autograd.Function):
@@ -28,10 +49,7 @@ class _AttnFn(torch.autograd.Function):
         lse = torch.empty((B * H * Lq,), device=q.device, dtype=torch.float32)
         seed = core.next_seed() if p_drop > 0 else 0
         scale = 1.0 / math.sqrt(dh)
-        core.check(core.lib().ldetr_attention_fwd_f32(
-            core.ptr(q), q.stride(0), core.ptr(k), k.stride(0), core.ptr(v), v.stride(0), core.ptr(kpm),
-            core.ptr(out), d, core.ptr(lse), B, H, Lq, Lk, dh, scale, p_drop, seed, core.seed_ptr() if p_drop > 0 else None,
-            0, core.stream()), 'attention_fwd')
+        _fwd(_fwd_args(q, k, v, kpm, out, lse, B, H, Lq, Lk, dh, scale, p_drop, seed, 0))
         ctx.save_for_backward(q, k, v, kpm, out, lse)
         ctx.cfg = (B, H, Lq, Lk, dh, scale, p_drop, seed)
         return out
@@ -73,13 +91,11 @@ class _AttnPackedFn(torch.autograd.Function):
         lse = torch.empty((B * H * L,), device=qkv.device, dtype=torch.float32)
         seed = core.next_seed() if p_drop > 0 else 0
         scale = 1.0 / math.sqrt(dh)
+        a = _fwd_args(q, k, v, kpm, out, lse, B, H, L, L, dh, scale, p_drop, seed, 1 if causal else 0)
         if rider.MODE is not None:      # an encoder stack in lock-step with another one: queued, or sent with the other's launch
-            rider.attention(q, k, v, kpm, out, lse, B, H, L, dh, scale, p_drop, seed, 1 if causal else 0)
+            rider.attention(a, out, lse)
         else:
-            core.check(core.lib().ldetr_attention_fwd_f32(
-                core.ptr(q), q.stride(0), core.ptr(k), k.stride(0), core.ptr(v), v.stride(0), core.ptr(kpm),
-                core.ptr(out), d, core.ptr(lse), B, H, L, L, dh, scale, p_drop, seed, core.seed_ptr() if p_drop > 0 else None,
-                1 if causal else 0, core.stream()), 'attention_fwd')
+            _fwd(a)
         ctx.save_for_backward(qkv, v_sep, kpm, out, lse)
         ctx.cfg = (B, H, L, dh, scale, p_drop, seed, 1 if causal else 0)
         return out

@@ -313,46 +313,49 @@ def gemm(A, B, ta, tb, M, N, K, out=None, ep=None, splitk=0, pix_per_sample=0, l
     require_gpu(A, B)
     if out is None:
         out = torch.empty((M, N), device=A.device, dtype=torch.float32)
+    if _rider is not None and _rider.MODE is not None and not ta and not tb and splitk == 0 and pix_per_sample == 0:
+        _rider.gemm(gemm_desc(A, B, 0, 0, M, N, K, out, ep, lda, ldb), out)      # an encoder stack in lock-step with another one: queued, or sent with the other's launch
+        return out
     lda = A.stride(0) if lda is None else lda
     ldb = B.stride(0) if ldb is None else ldb
-    if _rider is not None and _rider.MODE is not None and not ta and not tb and splitk == 0 and pix_per_sample == 0:
-        _rider.gemm(A, B, M, N, K, out, ep, lda, ldb)      # an encoder stack in lock-step with another one: queued, or sent with the other's launch
-        return out
     engine_call('gemm', 2.0 * M * N * K, lambda: check(lib().ldetr_gemm_f32(
         ptr(A), lda, int(ta), ptr(B), ldb, int(tb), ptr(out), out.stride(0), M, N, K, splitk,
         ctypes.byref(ep) if ep is not None else None, pix_per_sample, stream()), 'gemm'), nbytes=4.0 * (M * K + N * K + M * N))
     return out
 
 
-def _pair_descs(g0, g1):
-    descs = []
-    flops = 0.0
-    for g in (g0, g1):
-        require_gpu(g['A'], g['B'], g['out'])
-        d = _lib.GemmDesc()
-        d.A = g['A'].data_ptr(); d.lda = g['A'].stride(0); d.ta = int(g['ta'])
-        d.B = g['B'].data_ptr(); d.ldb = g['B'].stride(0); d.tb = int(g['tb'])
-        d.C = g['out'].data_ptr(); d.ldc = g['out'].stride(0)
-        d.M, d.N, d.K, d.splitk = int(g['M']), int(g['N']), int(g['K']), 0
-        d.ep = ctypes.addressof(g['ep']) if g.get('ep') is not None else None
-        d.pix_per_sample = 0
-        descs.append(d)
-        flops += 2.0 * d.M * d.N * d.K
-    return descs, flops
+def gemm_desc(A, B, ta, tb, M, N, K, out, ep=None, lda=None, ldb=None):
+    """ldetr_gemm_desc of out[M,N] = op(A) @ op(B) with the launch policy's split (splitk 0): the ONE place that assigns its fields, for the
+    pair, pair-forward and group entries."""
+    require_gpu(A, B, out)
+    d = _lib.GemmDesc()
+    d.A, d.lda, d.ta = A.data_ptr(), A.stride(0) if lda is None else lda, int(ta)
+    d.B, d.ldb, d.tb = B.data_ptr(), B.stride(0) if ldb is None else ldb, int(tb)
+    d.C, d.ldc = out.data_ptr(), out.stride(0)
+    d.M, d.N, d.K, d.splitk, d.pix_per_sample = int(M), int(N), int(K), 0, 0
+    d.ep = ctypes.addressof(ep) if ep is not None else None
+    if _rider is not None and _rider.MODE == 'record':
+        d._keep = (A, B, out, ep, getattr(ep, '_keep', None))      # a queued launch keeps its operands and what its epilogue points at alive
+    return d
+
+
+def _desc_of(g):
+    """gemm_desc of a problem given as dict(A, B, [ta, tb,] M, N, K, out, [ep])."""
+    return gemm_desc(g['A'], g['B'], g.get('ta', 0), g.get('tb', 0), g['M'], g['N'], g['K'], g['out'], g.get('ep'))
 
 
 def gemm_pair_is_single_launch(g0, g1):
     """True if gemm_pair(g0, g1) runs as one kernel launch."""
-    descs, _ = _pair_descs(g0, g1)
-    return lib().ldetr_gemm_pair_is_single_launch(ctypes.byref(descs[0]), ctypes.byref(descs[1])) == 1
+    return lib().ldetr_gemm_pair_is_single_launch(ctypes.byref(_desc_of(g0)), ctypes.byref(_desc_of(g1))) == 1
 
 
 def gemm_pair(g0, g1):
     """Two gemm() calls as one C-ABI call (ldetr_gemm_pair_f32): g = dict(A, B, ta, tb, M, N, K, out, ep).
     The data and the weight gradient of a linear layer (or the two weight gradients of the fused feed-forward block) run as ONE kernel
     launch when both are small-tile problems; otherwise as two, in order."""
-    descs, flops = _pair_descs(g0, g1)
-    engine_call('gemm', flops, lambda: check(lib().ldetr_gemm_pair_f32(ctypes.byref(descs[0]), ctypes.byref(descs[1]), stream()), 'gemm_pair'),
+    descs = [_desc_of(g0), _desc_of(g1)]
+    engine_call('gemm', sum(2.0 * d.M * d.N * d.K for d in descs),
+                lambda: check(lib().ldetr_gemm_pair_f32(ctypes.byref(descs[0]), ctypes.byref(descs[1]), stream()), 'gemm_pair'),
                 nbytes=4.0 * sum(d.M * d.K + d.N * d.K + d.M * d.N for d in descs))
 
 
@@ -367,18 +370,9 @@ def gemm_group(problems, post=None):
     n = len(problems)
     if n < 1 or n > GEMM_GROUP_MAX:
         return False
-    descs = (_lib.GemmDesc * n)()
-    flops = nbytes = 0.0
-    for d, g in zip(descs, problems):
-        require_gpu(g['A'], g['B'], g['out'])
-        d.A = g['A'].data_ptr(); d.lda = g['A'].stride(0); d.ta = 0
-        d.B = g['B'].data_ptr(); d.ldb = g['B'].stride(0); d.tb = 0
-        d.C = g['out'].data_ptr(); d.ldc = g['out'].stride(0)
-        d.M, d.N, d.K, d.splitk = int(g['M']), int(g['N']), int(g['K']), 0
-        d.ep = ctypes.addressof(g['ep']) if g.get('ep') is not None else None
-        d.pix_per_sample = 0
-        flops += 2.0 * d.M * d.N * d.K
-        nbytes += 4.0 * (d.M * d.K + d.N * d.K + d.M * d.N)
+    descs = (_lib.GemmDesc * n)(*[gemm_desc(g['A'], g['B'], 0, 0, g['M'], g['N'], g['K'], g['out'], g.get('ep')) for g in problems])
+    flops = sum(2.0 * d.M * d.N * d.K for d in descs)
+    nbytes = 4.0 * sum(d.M * d.K + d.N * d.K + d.M * d.N for d in descs)
     scales = (ctypes.c_float * n)(*[float(v) for v in post]) if post is not None else None
     rc = engine_call('gemm', flops, lambda: lib().ldetr_gemm_small_group_f32(descs, scales, n, stream()), nbytes=nbytes)
     if rc == 3:              # LDETR_ERR_UNSUPPORTED: not a group the library runs as one launch

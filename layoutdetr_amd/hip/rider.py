@@ -46,9 +46,9 @@ def _take(kind):
 def _send_alone(p):
     l = core.lib()
     if p.kind == 'gemm':
-        d, ep = p.args, p.keep[3]
-        core.check(l.ldetr_gemm_f32(ctypes.c_void_p(d.A), d.lda, 0, ctypes.c_void_p(d.B), d.ldb, 0, ctypes.c_void_p(d.C), d.ldc, d.M, d.N, d.K, 0,
-                                    ctypes.byref(ep) if ep is not None else None, 0, core.stream()), 'gemm')
+        d = p.args
+        ep = ctypes.cast(d.ep, ctypes.POINTER(_lib.Epilogue)) if d.ep else None
+        core.check(l.ldetr_gemm_f32(d.A, d.lda, 0, d.B, d.ldb, 0, d.C, d.ldc, d.M, d.N, d.K, 0, ep, 0, core.stream()), 'gemm')
     elif p.kind == 'attention':
         core.check(l.ldetr_attention_fwd_group_f32(ctypes.byref(p.args), 1, core.stream()), 'attention_fwd')
     else:
@@ -84,26 +84,14 @@ def _send(me):
     STATS['paired'] += 1
 
 
-def gemm(A, B, M, N, K, out, ep, lda, ldb):
-    """hip.core.gemm's launch of an NT problem while a mode is set."""
-    d = _lib.GemmDesc()
-    d.A, d.lda, d.ta, d.B, d.ldb, d.tb = A.data_ptr(), lda, 0, B.data_ptr(), ldb, 0
-    d.C, d.ldc, d.M, d.N, d.K, d.splitk = out.data_ptr(), out.stride(0), int(M), int(N), int(K), 0
-    d.ep = ctypes.addressof(ep) if ep is not None else None
-    d.pix_per_sample = 0
-    _send(_Pending('gemm', d, (A, B, out, ep, getattr(ep, '_keep', None)), outs=(out,)))
+def gemm(d, out):
+    """hip.core.gemm's launch of an NT problem (its core.gemm_desc, which holds the operands while it is queued) while a mode is set."""
+    _send(_Pending('gemm', d, getattr(d, '_keep', None), outs=(out,)))
 
 
-def attention(q, k, v, kpm, out, lse, B, H, L, dh, scale, p_drop, seed, causal):
-    """hip.attention's packed self-attention forward launch while a mode is set."""
-    a = _lib.AttnArgs()
-    a.q, a.ldq, a.k, a.ldk, a.v, a.ldv = q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0)
-    a.key_padding_mask = kpm.data_ptr() if kpm is not None else None
-    a.out, a.ldo, a.lse = out.data_ptr(), out.stride(0), lse.data_ptr()
-    a.B, a.H, a.Lq, a.Lk, a.head_dim, a.scale, a.p_drop, a.seed = B, H, L, L, dh, scale, p_drop, seed
-    a.seed_ptr = core.iter_seed().data_ptr() if p_drop > 0 else None
-    a.causal = causal
-    _send(_Pending('attention', a, (q, k, v, kpm, out, lse), outs=(out, lse)))
+def attention(a, out, lse):
+    """hip.attention's packed self-attention forward launch (its argument block, which holds the tensors) while a mode is set."""
+    _send(_Pending('attention', a, a._keep, outs=(out, lse)))
 
 
 def takes_block(what, args):

@@ -43,7 +43,7 @@ def _gemm_problem(M, N, K, kind, seed, dev):
 
 @pytest.mark.parametrize('K,kinds', [(256, ('bias', 'relu_drop')), (256, ('relu_drop', 'residual')), (256, ('residual', 'bias')), (1024, ('bias', 'relu_drop'))])
 def test_gemm_pair_fwd_bit_equal_to_single_launches(dev, K, kinds):
-    """M = 35 and 70 (no multiple of the 32-row tile, different per half), N = 256.  K = 1024 on 16 / 24 tiles is the case plan_small_split
+    """M = 35 and 70 (no multiple of the 32-row tile, different per half), N = 256.  K = 1024 on 16 / 24 tiles is the case small_plan_rule
     splits (tiles <= 128 and K >= 1024 -> K / 256 = 4 slices each, 4 x 24 <= 640): asserted from the launch record."""
     from layoutdetr_amd.hip import core
     core.iter_seed(dev).fill_(987654321)
@@ -58,7 +58,7 @@ def test_gemm_pair_fwd_bit_equal_to_single_launches(dev, K, kinds):
         buf, view = _padded(p['M'], p['N'], dev)
         p['out'], p['ep'], p['ta'], p['tb'] = view, ep, 0, 0
         paired.append(buf)
-    descs, _ = core._pair_descs(probs[0], probs[1])
+    descs = [core.gemm_desc(p['A'], p['B'], 0, 0, p['M'], p['N'], p['K'], p['out'], p['ep']) for p in probs]
     rc = core.lib().ldetr_gemm_pair_fwd_f32(ctypes.byref(descs[0]), ctypes.byref(descs[1]), core.stream())
     assert rc == 0, 'the two problems must go out as one launch'
     info = (ctypes.c_int32 * 10)()
@@ -84,14 +84,10 @@ def _attn_problem(B, L, seed, dev):
 
 
 def _attn_args(p, out, lse, dev):
-    from layoutdetr_amd import _lib
-    from layoutdetr_amd.hip import core
-    a = _lib.AttnArgs()
+    from layoutdetr_amd.hip import attention, core
     q, k, v = p['qkv'][:, :256], p['qkv'][:, 256:512], p['qkv'][:, 512:]
-    a.q, a.ldq, a.k, a.ldk, a.v, a.ldv = q.data_ptr(), 768, k.data_ptr(), 768, v.data_ptr(), 768
-    a.key_padding_mask, a.out, a.ldo, a.lse = p['kpm'].data_ptr(), out.data_ptr(), out.stride(0), lse.data_ptr()
-    a.B, a.H, a.Lq, a.Lk, a.head_dim, a.scale, a.p_drop, a.seed = p['B'], 8, p['L'], p['L'], 32, 32 ** -0.5, 0.1, p['seed']
-    a.seed_ptr, a.causal = core.iter_seed(dev).data_ptr(), 0
+    a = attention._fwd_args(q, k, v, p['kpm'], out, lse, p['B'], 8, p['L'], p['L'], 32, 32 ** -0.5, 0.1, p['seed'], 0)
+    assert (a.ldq, a.ldk, a.ldv) == (768, 768, 768) and a.seed_ptr == core.iter_seed(dev).data_ptr()
     return a
 
 

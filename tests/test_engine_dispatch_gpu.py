@@ -179,7 +179,7 @@ CASES = {
     'gemm_nn_70x36x52': dense(70, 36, 52, 0, 1),                 # launch_small<0, 1>, generic loads
     'gemm_tn_70x36x52': dense(70, 36, 52, 1, 1),                 # launch_small<1, 1>, generic loads
     'gemm_nt_144x256x256': dense(144, 256, 256, 0, 0),           # launch_small<0, 0>, FAST
-    'gemm_nt_144x256x2048': dense(144, 256, 2048, 0, 0),         # launch_small<0, 0> with plan_small_split's in-kernel split-K (workspace slice)
+    'gemm_nt_144x256x2048': dense(144, 256, 2048, 0, 0),         # launch_small<0, 0> with small_plan_rule's in-kernel split-K (workspace slice)
     'gemm_nt_4096x256x64': dense(4096, 256, 64, 0, 0),           # launch_gemm<OP_KC_DENSE, OP_KC_DENSE>: exactly SMALL_GEMM_TILES tiles
     'gemm_nn_4096x256x64': dense(4096, 256, 64, 0, 1),           # launch_gemm<OP_KC_DENSE, OP_RC_DENSE>
     'gemm_splitk8_epilogue_workspace': dense_splitk_epilogue(True),        # launch_gemm: fix-up slice from the ring

@@ -698,6 +698,78 @@ def test_gemm_pair_single_launch_predicate():
     assert lib.ldetr_gemm_pair_is_single_launch(None, None) == 0
 
 
+def test_multi_problem_entries_refuse_before_launching():
+    """The refusals of ldetr_gemm_pair_fwd_f32, ldetr_gemm_small_group_f32 and ldetr_attention_fwd_group_f32 (pure host code: each returns before
+    the first launch and before a workspace slice is taken, so fake addresses do): LDETR_ERR_UNSUPPORTED (3) with the message that names the
+    reason where the caller is to issue the problems singly, LDETR_ERR_ARG (1) where the call itself is malformed."""
+    import ctypes
+    from layoutdetr_amd import _lib
+    lib = _lib.load()
+
+    def ep(**kw):
+        e = _lib.Epilogue()
+        e.alpha = 1.0; e.out_scale = 1.0; e.act_gain = 1.0
+        for k, v in kw.items():
+            setattr(e, k, v)
+        return e
+
+    def desc(M, N, K, ta=0, tb=0, splitk=0, ep=None):
+        g = _lib.GemmDesc()
+        g.A, g.B, g.C = 0x1000, 0x2000, 0x3000     # fake 16-byte aligned addresses: a refusal reads no memory
+        g.ta, g.tb, g.M, g.N, g.K, g.splitk = ta, tb, M, N, K, splitk
+        g.lda = M if ta else K
+        g.ldb = N if tb else K
+        g.ldc = N
+        g.ep = ctypes.addressof(ep) if ep is not None else None
+        return g
+
+    def refused(rc, code, phrase):
+        msg = lib.ldetr_last_error().decode()
+        assert rc == code and phrase in msg, (rc, msg)
+
+    # two nn.Linear-shaped halves as one launch of the pair kernel
+    base = desc(35, 256, 256)
+    pair = lambda g1: lib.ldetr_gemm_pair_fwd_f32(ctypes.byref(base), ctypes.byref(g1), None)
+    rowsum = ep(a_rowsum=4096)
+    for g1 in (desc(35, 256, 256, ta=1), desc(35, 256, 256, splitk=2), desc(4096, 1024, 512), desc(35, 256, 256, ep=rowsum)):
+        refused(pair(g1), 3, 'problem 1 is not an NT small-tile problem')
+    refused(pair(desc(35, 256, 48)), 3, '(FAST)')             # K % 32 != 0: not FAST, the first half is
+    refused(pair(desc(16, 32, 512)), 3, '(waves)')            # one tile with 512 of K: 8 waves; the first half (16 tiles, 256 of K): 4
+    refused(lib.ldetr_gemm_pair_fwd_f32(None, ctypes.byref(base), None), 1, 'null descriptor')
+    refused(lib.ldetr_gemm_pair_fwd_f32(ctypes.byref(base), None, None), 1, 'null descriptor')
+
+    # the grouped launch of plain NN problems
+    def group(*gs, n=None):
+        arr = (_lib.GemmDesc * max(len(gs), 1))(*gs)
+        return lib.ldetr_gemm_small_group_f32(arr, None, len(gs) if n is None else n, None)
+    refused(group(n=0), 1, '1..32 problems')
+    refused(group(*[desc(3, 32, 32) for _ in range(33)]), 1, '1..32 problems')
+    refused(group(desc(3, 32, 1024)), 3, 'problem 0 splits its reduction')
+    relu = ep(act=1)
+    refused(group(desc(3, 32, 32), desc(3, 32, 32, tb=1)), 3, 'problem 1 is not a plain NN small-tile problem')
+    refused(group(desc(3, 32, 32, ep=relu)), 3, 'problem 0 is not a plain NN small-tile problem')
+    refused(group(desc(3, 32, 32), desc(16, 32, 512)), 3, 'another instantiation')
+
+    # two attention problems as one launch
+    def attn(Lq, Lk=None, dh=32, causal=0):
+        a = _lib.AttnArgs()
+        a.q, a.k, a.v, a.out, a.lse = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000
+        a.ldq = a.ldk = a.ldv = 768
+        a.ldo = 256
+        a.B, a.H, a.Lq, a.Lk, a.head_dim, a.scale, a.causal = 1, 8, Lq, Lq if Lk is None else Lk, dh, 32 ** -0.5, causal
+        return a
+
+    def attn_group(*ps):
+        return lib.ldetr_attention_fwd_group_f32((_lib.AttnArgs * len(ps))(*ps), len(ps), None)
+    refused(attn_group(attn(35), attn(35), attn(35)), 1, '1 or 2 problems')
+    refused(attn_group(attn(35), attn(35, dh=64)), 3, '32-wide heads only')
+    different = 'resolve to different kernels'
+    refused(attn_group(attn(35), attn(64)), 3, different)     # attn_fwd_kernel next to attn_fwd_wide_kernel
+    refused(attn_group(attn(35), attn(20)), 3, different)     # 4 key tiles next to 2
+    refused(attn_group(attn(300), attn(300)), 3, different)   # the long-key kernel has no two-problem form
+    refused(attn_group(attn(35), attn(35, Lk=20, causal=1)), 1, 'causal mask is defined for self-attention')
+
+
 def test_backward_stage_count_and_two_stage_segments(monkeypatch):
     """training_loop.backward_stage_count (trunk | rest at <= 4 samples per GPU, three stages above, LDETR_BACKWARD_STAGES overrides) and
     FlatModule.stage_segments(2): the two-stage segments tile the flat buffer and merge the three-stage trunk segments."""
